@@ -1,8 +1,16 @@
 #!/usr/bin/env python3
 """Headline benchmark: list entries sampled+verified per second at n = 11.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(metric, value, ms_per_step, the roofline arithmetic of the timed steps).
+--full adds everything that costs time of its own after the timed region: the
+CPU baselines (every config), the verification block (golden counts, device
+row checksums) and the PMC-derived roofline.traffic / roofline.issue figures.
+--dump-outputs DIR writes what the last timed step of the headline returned
+(see dump_outputs) for comparing two builds output for output.
 
 `python bench.py --gpus N` outside torchrun launches the N ranks itself (one
 process per GPU under torch.distributed.run, see launch_ranks) and prints rank
@@ -53,7 +61,7 @@ timed launches (device time / K): an event pair around every launch costs
 10.4 us gaps before each list kernel, none with one pair), which would be
 charged to the step.  QBA_BENCH_EVENTS=step restores the per-launch pairs.
 
-verification (outside the timed region): the all-reduced H, C, P against
+verification (--full; outside the timed region): the all-reduced H, C, P against
 the C twin's totals of entries [0, N x 1.25e8) (counts_equal_golden; at N = 8
 counts_equal_1e9_golden), position-weighted checksums of every row each rank
 wrote, computed on the device, against the C twin's checksums of that shard
@@ -97,7 +105,12 @@ def parse():
                     help="list rows as nibbles (qba_*_packed, the shipped hot path) or one byte per value")
     ap.add_argument("--seed", type=int, default=0x5EED)
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-baseline work")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: CPU baselines, the verification "
+                         "block (golden counts, row checksums), PMC-derived roofline.traffic / roofline.issue")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="headline only: write the last timed step's outputs to DIR/<name>.npy")
     ap.add_argument("--sv-qubits", type=int, default=None, help="--config 4 register size")
     ap.add_argument("--traffic", default=str(ROOT / "profiles" / "traffic_n11.json"),
                     help="PMC-derived HBM bytes per launch (profiles/), if present")
@@ -235,6 +248,45 @@ def verify_rows(n, seed, per, sums):
     return {"rows_equal_golden": all(same), "rows_equal_golden_per_rank": same,
             "rows_golden": f"C-twin row sums (sum L_g[k], sum L_g[k]*(k+1)) of every rank's shard rows "
                            f"(tests/golden/{GOLDEN_ROWS.name})"}
+
+
+DUMP_EDGE, DUMP_SAMPLE, DUMP_SEED = 4096, 1 << 19, 0xD0B5
+
+
+def dump_columns(count):
+    """The entries of a step whose list values --dump-outputs writes: the
+    first and last DUMP_EDGE and DUMP_SAMPLE drawn with a fixed seed, sorted,
+    each once (every entry when the step has no more than that)."""
+    import numpy as np
+    if count <= 2 * DUMP_EDGE + DUMP_SAMPLE:
+        return np.arange(count, dtype=np.int64)
+    edge = np.arange(DUMP_EDGE, dtype=np.int64)
+    drawn = np.random.default_rng(DUMP_SEED).integers(0, count, DUMP_SAMPLE, dtype=np.int64)
+    return np.unique(np.concatenate([edge, drawn, count - DUMP_EDGE + edge]))
+
+
+def dump_outputs(out_dir, lists, n, count, packed, H, C, P):
+    """--dump-outputs: what the last timed step returned to its caller, as
+    DIR/<name>.npy.  counts_H / counts_C / counts_P: the (all-reduced) count
+    tables in float64 (exact: every count is below 2^53).  lists_sample: the
+    n+1 list values of the entries dump_columns names, float32 [n+1, m], read
+    from the rows as stored (nibble rows: entry 2b = the low nibble of byte
+    b); lists_sample_index: those entries' positions in this rank's shard,
+    float64.  ~30 MB at the headline size.  Outside the timed region."""
+    import numpy as np
+    import torch
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, x in (("counts_H", H), ("counts_C", C), ("counts_P", P)):
+        np.save(d / f"{name}.npy", x.cpu().numpy().astype(np.float64))
+    cols = dump_columns(count)
+    k = torch.from_numpy(cols).to(lists.device)
+    if packed:
+        vals = (lists[:n + 1].index_select(1, k >> 1).to(torch.int32) >> ((k & 1) * 4).to(torch.int32)) & 15
+    else:
+        vals = lists[:n + 1].index_select(1, k)
+    np.save(d / "lists_sample.npy", vals.cpu().numpy().astype(np.float32))
+    np.save(d / "lists_sample_index.npy", cols.astype(np.float64))
 
 
 # Measured issue cost per wave64 VALU instruction on one SIMD at 8 waves
@@ -422,21 +474,22 @@ def headline(args):
     else:
         rank_ms = [kern_ms]
 
-    # verification result of the last step (the all-reduced counts): honest Q
-    # positions never collide, and against the C twin's totals when recorded
-    Hn, Cn, Pn = (x.cpu().numpy() for x in (H, C, P))
-    # ... and the rows it wrote (every step writes the same rows): checksums on
-    # the device, gathered from every rank
-    rs = device_row_sums(lists, n, per, packed)
-    if world > 1:
-        gathered = [torch.zeros_like(rs) for _ in range(world)]
-        torch.distributed.all_gather(gathered, rs)
-        row_sums = [x.cpu().numpy() for x in gathered]
-    else:
-        row_sums = [rs.cpu().numpy()]
+    row_sums = None
+    if args.full:
+        # the rows the last step wrote (every step writes the same rows):
+        # checksums on the device, gathered from every rank
+        rs = device_row_sums(lists, n, per, packed)
+        if world > 1:
+            gathered = [torch.zeros_like(rs) for _ in range(world)]
+            torch.distributed.all_gather(gathered, rs)
+            row_sums = [x.cpu().numpy() for x in gathered]
+        else:
+            row_sums = [rs.cpu().numpy()]
     if rank != 0:
         eng.close()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, lists, n, per, packed, H, C, P)
     entries = per * world * args.steps
     value = entries / t_max
     bytes_per_entry = 2 * (n + 1)  # BASELINE's scoring convention (metric_scale)
@@ -448,7 +501,9 @@ def headline(args):
     metric_gbs = bytes_per_entry * per / (kern_ms * 1e-3) / 1e9
     traffic, traffic_note, issue = None, "no PMC traffic file for this workload", None
     tp = Path(args.traffic)
-    if tp.exists():
+    if not args.full:
+        traffic_note = "not read (--full)"
+    elif tp.exists():
         tj = json.loads(tp.read_text())
         sha = _lib_sha16()
         if tj.get("per_launch_entries") == per and tj.get("n") == n and tj.get("mode") == args.mode and \
@@ -511,12 +566,16 @@ def headline(args):
                                      "not a physical fraction (can pass 1)"},
             "issue": issue,
         },
-        "verification": {**verify_counts(n, args.seed, per, world, Hn, Cn, Pn),
-                         **verify_rows(n, args.seed, per, row_sums),
-                         "allreduce_ranks": ranks_seen, "backend": backend},
         "rank_launch_ms": {"min": min(rank_ms), "max": max(rank_ms), "per_rank": rank_ms},
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        # verification result of the last step (the all-reduced counts): honest Q
+        # positions never collide, and against the C twin's totals when recorded
+        Hn, Cn, Pn = (x.cpu().numpy() for x in (H, C, P))
+        out["verification"] = {**verify_counts(n, args.seed, per, world, Hn, Cn, Pn),
+                               **verify_rows(n, args.seed, per, row_sums),
+                               "allreduce_ranks": ranks_seen, "backend": backend}
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_counts(n, args.seed, info, args.cpu_seconds)
     print(json.dumps(out), flush=True)
     eng.close()
@@ -552,7 +611,7 @@ def config0(args, eng):
     extra = {"ms_per_step": dt * 1e3,
              "protocol": {"success": [r.result["success"] for r in runs[:5]],
                           "messages": runs[0].messages, "bytes": runs[0].bytes}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         sys.path.insert(0, str(ROOT / "oracle"))
         sys.path.insert(0, str(ROOT / "tests"))
         from oracle_engine import OracleEngine  # numpy restatement (test infrastructure)
@@ -648,7 +707,7 @@ def config1(args, eng):
              "reduction": "deferred: step k's counts reduced inside step k+1's list kernel, the last by "
                           "the flush at the end of the graph (qba_sample_check_packed_deferred)",
              "verification": {"deferred_counts_equal_sync": bool(same)}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         extra["cpu_baseline"] = cpu_baseline_counts(n, args.seed, info, args.cpu_seconds / 2)
     return _line(args, count / wall, "entries/s",
                  "BASELINE configs[1]: n=11 parties, 3 dishonest, sizeL=1e6 on one GPU "
@@ -688,7 +747,7 @@ def config3(args, eng, n_inst=4096, count=100_000):
     # C[u][g][g] = |P_u| on the diagonal, 0 off it for honest lists
     honest = bool((c.C.sum((1, 2, 3)) == c.P.sum(1) * (n + 1)).all().item())
     extra = {"ms_per_step": wall * 1e3, "verification": {"all_instances_collision_free": honest}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         extra["cpu_baseline"] = cpu_baseline_batched(n, args.seed, count, eng.prepare(n), args.cpu_seconds)
     return _line(args, ent / wall, "entries/s",
                  f"BASELINE configs[3]: {n_inst} independent n=7 instances x sizeL={count} per GPU",
@@ -887,6 +946,8 @@ def main():
         return
     if args.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
         raise SystemExit("--config 0/1/3/4 are single-GPU measurements")
+    if args.dump_outputs:
+        raise SystemExit("--dump-outputs writes the headline's outputs (--config 2)")
     import torch
     torch.cuda.set_device(0)
     eng = importlib.import_module(f"{PKG}.engine").Engine(0)

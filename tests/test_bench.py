@@ -51,7 +51,7 @@ def test_bench_self_launch_two_ranks_gpu():
     honest lists verified collision-free."""
     env = _env(QBA_SHARE_DEVICE="1", QBA_DIST_BACKEND="gloo", QBA_BENCH_LAUNCH_TIMEOUT="150")
     p = subprocess.run([sys.executable, "-u", str(ROOT / "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=180)
+                        "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=180)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = _json_lines(p.stdout)
     assert len(lines) == 1, p.stdout
@@ -144,6 +144,92 @@ def test_row_sums_of_stored_rows_match_c_twin(count):
     byte = np.zeros((n + 1, count + 5), np.uint8)
     byte[:, :count] = L
     assert np.array_equal(b.device_row_sums(torch.from_numpy(byte), n, count, False).numpy(), want.astype(np.int64))
+
+
+def test_dump_columns_fixed_and_bounded():
+    """--dump-outputs' sample of a large step: the same entries on every call,
+    sorted, each once, both edges included, and small enough that the dumped
+    list values (12 rows of float32) stay far below 64 MB."""
+    import numpy as np
+    b = _bench_mod()
+    count = 125_000_000
+    cols = b.dump_columns(count)
+    assert np.array_equal(cols, b.dump_columns(count))
+    assert cols.dtype == np.int64 and np.all(np.diff(cols) > 0) and cols[0] == 0 and cols[-1] == count - 1
+    assert np.array_equal(cols[:b.DUMP_EDGE], np.arange(b.DUMP_EDGE))
+    assert np.array_equal(cols[-b.DUMP_EDGE:], np.arange(count - b.DUMP_EDGE, count))
+    assert b.DUMP_SAMPLE // 2 < len(cols) <= 2 * b.DUMP_EDGE + b.DUMP_SAMPLE
+    assert 12 * len(cols) * 4 + len(cols) * 8 < 32 << 20
+    small = 2 * b.DUMP_EDGE + b.DUMP_SAMPLE
+    assert np.array_equal(b.dump_columns(small), np.arange(small))
+    assert len(b.dump_columns(small + 1)) < small + 1
+
+
+@pytest.mark.parametrize("count", [1, 4099, 100_003])
+def test_dump_outputs_of_stored_rows(tmp_path, count):
+    """bench.dump_outputs (run here on CPU tensors) writes the C twin's list
+    values of the sampled entries from nibble rows and from byte rows, and the
+    count tables unchanged, as float32 / float64 .npy files."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, str(ROOT / "oracle"))
+    import oracle_lib
+    b = _bench_mod()
+    empty = {"nfac": 0, "desc": np.zeros((16, 6), np.int32), "pat": np.zeros(1, np.uint64),
+             "apat": np.zeros(1, np.uint64), "thr": np.zeros(1, np.uint64)}
+    n, seed, first = 11, 0x5EED, 10
+    L = oracle_lib.sample(n, seed, first, count, empty, empty, True)
+    H, C, P, _ = oracle_lib.counts(L, n)
+    nb = (count + 1) // 2
+    pk = np.zeros((n + 1, nb + 7), np.uint8)
+    pk[:, : count // 2] = L[:, 0:count - count % 2:2] | (L[:, 1::2][:, : count // 2] << 4)
+    if count % 2:
+        pk[:, nb - 1] = L[:, -1]
+    byte = np.zeros((n + 1, count + 5), np.uint8)
+    byte[:, :count] = L
+    t = [torch.from_numpy(np.asarray(x).astype(np.int64)) for x in (H, C, P)]
+    for name, rows, packed in (("p", pk, True), ("b", byte, False)):
+        b.dump_outputs(tmp_path / name, torch.from_numpy(rows), n, count, packed, *t)
+        got = {f.stem: np.load(f) for f in (tmp_path / name).iterdir()}
+        assert sorted(got) == ["counts_C", "counts_H", "counts_P", "lists_sample", "lists_sample_index"]
+        assert got["lists_sample"].dtype == np.float32 and got["lists_sample_index"].dtype == np.float64
+        assert np.array_equal(got["lists_sample_index"], np.arange(count))
+        assert np.array_equal(got["lists_sample"], L.astype(np.float32))
+        for key, want in (("counts_H", H), ("counts_C", C), ("counts_P", P)):
+            assert got[key].dtype == np.float64 and np.array_equal(got[key], np.asarray(want, np.float64))
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run of the headline path (a small shard, 3 timed steps): the
+    result line has the headline's keys and none of --full's blocks, and
+    --dump-outputs holds the last step's lists and counts, equal to the C
+    twin's (every entry: the shard is below the sampling threshold)."""
+    import numpy as np
+    sys.path.insert(0, str(ROOT / "oracle"))
+    import oracle_lib
+    n, seed, count = 11, 0x5EED, 100_003
+    p = subprocess.run([sys.executable, "-u", str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--per-gpu", str(count), "--dump-outputs", str(tmp_path / "d")],
+                       env=_env(), capture_output=True, text=True, timeout=180)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = _json_lines(p.stdout)
+    assert len(lines) == 1, p.stdout
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "entries/s" and line["higher_is_better"] is True and line["dtype"].startswith("u4")
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 / count - 1) < 1e-9
+    assert "verification" not in line and "cpu_baseline" not in line and line["roofline"]["issue"] is None
+    empty = {"nfac": 0, "desc": np.zeros((16, 6), np.int32), "pat": np.zeros(1, np.uint64),
+             "apat": np.zeros(1, np.uint64), "thr": np.zeros(1, np.uint64)}
+    L = oracle_lib.sample(n, seed, 0, count, empty, empty, True)
+    H, C, P, bad = oracle_lib.counts(L, n)
+    got = {f.stem: np.load(f) for f in (tmp_path / "d").iterdir()}
+    assert bad == 0 and got["lists_sample"].dtype == np.float32
+    assert np.array_equal(got["lists_sample"], L.astype(np.float32))
+    assert np.array_equal(got["lists_sample_index"], np.arange(count))
+    for key, want in (("counts_H", H), ("counts_C", C), ("counts_P", P)):
+        assert got[key].dtype == np.float64 and np.array_equal(got[key], np.asarray(want, np.float64)), key
 
 
 def test_row_golden_verification_cpu():

@@ -2,8 +2,8 @@
 # One GPU call, steps chosen on the command line (run in the order given):
 #   tools/gpu_round.sh <tag> [steps...]
 #     tests   pytest -m gpu (whole GPU suite)       smoke   __graft_entry__.smoke()
-#     bench   the driver's command (N=1, --steps 20 --warmup 5), twice
-#     long    bench.py defaults (50 + 200 launches)  c0 c1 c3 c4   bench.py --config k
+#     bench   the driver's command (N=1, --steps 20 --warmup 5) with --full, twice
+#     long    bench.py --full defaults (50 + 200 launches)  c0 c1 c3 c4   bench.py --config k --full
 #     prof    rocprofv3 --kernel-trace --stats of the driver's command (+ tools/trace_check.py)
 #     profc1  the same for --config 1        profc3  ... for --config 3
 #     pmc     tools/pmc.sh passes of the headline + tools/pmc_traffic.py -> pmc/traffic.json
@@ -27,10 +27,10 @@ for s in $steps; do
              > "$out/pytest.log" 2>&1; tail -3 "$out/pytest.log" ;;
     smoke) timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1 ;;
     bench) for i in 1 2; do
-             timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 > "$out/bench_driver$i.json" \
+             timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > "$out/bench_driver$i.json" \
                2> "$out/bench_driver$i.err"; done ;;
-    long) timeout -k 10 300 python -u bench.py > "$out/bench_long.json" 2> "$out/bench_long.err" ;;
-    c0|c1|c3|c4) timeout -k 10 400 python -u bench.py --config ${s#c} > "$out/bench_config${s#c}.json" \
+    long) timeout -k 10 300 python -u bench.py --full > "$out/bench_long.json" 2> "$out/bench_long.err" ;;
+    c0|c1|c3|c4) timeout -k 10 400 python -u bench.py --config ${s#c} --full > "$out/bench_config${s#c}.json" \
                    2> "$out/bench_config${s#c}.err" ;;
     prof) (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof" -o bench \
              -- python "$root/bench.py" --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$out/prof_bench.json" \

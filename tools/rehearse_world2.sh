@@ -9,4 +9,4 @@ out=$root/gpurun_out/world2; mkdir -p $out
 cd $root
 QBA_SHARE_DEVICE=1 QBA_DIST_BACKEND=gloo timeout -k 10 240 python -m torch.distributed.run --nnodes=1 \
   --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 \
-  --per-gpu 2.5e7 > $out/bench.json 2> $out/bench.err
+  --per-gpu 2.5e7 --full > $out/bench.json 2> $out/bench.err
