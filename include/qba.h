@@ -235,6 +235,28 @@ QBA_API int qba_sample_check_batched_packed(qba_ctx *ctx, int n_parties, uint64_
                                             uint64_t ld, uint64_t inst_stride, int64_t *H_dev,
                                             int64_t *C_dev, int64_t *P_dev, qba_stream stream);
 
+/* The protocol rounds of the batched instances, decided on the device from
+ * their count tables (H_dev, C_dev, P_dev in the layout of
+ * qba_sample_check_batched): replaces, per instance, the dishonest draw
+ * (tfg.py:101-125), the commander's broadcast (166-196), the lieutenants'
+ * rounds and decisions (266-306) and the round loop with its Success line
+ * (337-363), in count mode's canonical order with barrier-epoch delivery.
+ * Rank r of instance i draws from the Philox stream keyed seed_base + i
+ * (csrc/qba_internal.h; disjoint from the sampler's counters), so the result
+ * is the one of montecarlo.run_host, field by field.  Instance i writes
+ * 4 + 5*(n+1) int32 at out_dev + i*(4 + 5*(n+1)):
+ *   {success, dishonest-rank bitmask, empty-V_i rank bitmask, status}, then
+ *   per rank r = 0..n {decision (-1 on an empty V_i), V_r bitmask, accept,
+ *   reject, sent}  (rank 0: zeros; the commander's V is 0).
+ * status bit 0 = a mailbox overflowed, bit 1 = an RNG retry cap (64 words) was
+ * hit; with a nonzero status every other field of the instance is 0.
+ * 1 <= n_parties <= 15 and 0 <= n_dishonest <= n_parties, else QBA_EINVAL
+ * (checked before ctx, which may then be NULL).  One launch per 2^20
+ * instances; asynchronous on `stream`, allocates nothing. */
+QBA_API int qba_protocol_batched(qba_ctx *ctx, int n_parties, int n_dishonest, uint64_t seed_base,
+                                 int64_t n_instances, const int64_t *H_dev, const int64_t *C_dev,
+                                 const int64_t *P_dev, int32_t *out_dev, qba_stream stream);
+
 /* ---- (A5-A8) checks, exact-order mode (bit-exact protocol parity) --------------- */
 /* isQCorrList = {k : Li[k] != Lc[k]} (tfg.py:327) as ascending indices.
  * *count_host receives the number found; at most `cap` are written. Synchronous. */

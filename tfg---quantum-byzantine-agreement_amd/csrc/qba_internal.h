@@ -90,6 +90,20 @@ __device__ __forceinline__ QbaU4 qba_philox(uint32_t c0, uint32_t c1, uint32_t c
 // is not uniform a 32-bit u from its own word u_word: outcome pattern
 // = (u < thr[col]) ? pat[col] : apat[col].
 // ---------------------------------------------------------------------------
+//
+// Protocol streams (qba_proto.hip, montecarlo.ProtocolRng): word t of rank r
+// (0 = QSD, 1 = commander, >= 2 = lieutenants) of the instance keyed
+// key = seed_base + i is output word t % 4 of
+//   philox(ctr = {t / 4, r, 0, QBA_PROTO_CTR_TAG}, key = {key_lo, key_hi}).
+// Disjoint from the sampler's counters above under the same key: their word 3
+// is only ever 0 (entry blocks, retry blocks) or 1 (oracle/sampler_ref.c:75,
+// 169, 200).
+// ---------------------------------------------------------------------------
+#define QBA_PROTO_CTR_TAG 0x51424150u
+#define QBA_PROTO_RNG_CAP 64      // words one randint may draw; extra draws of `while v2 == v1`
+#define QBA_PROTO_ST_MAILBOX 1u   // status bit 0: a (dest, src) mailbox was full
+#define QBA_PROTO_ST_RNG 2u       // status bit 1: an RNG retry cap was hit
+
 struct QbaFactor {
   int32_t bits;
   int32_t uniform;

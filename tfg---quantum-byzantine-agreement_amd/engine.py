@@ -256,6 +256,29 @@ class Engine:
              self.stream())
         return lists, counts
 
+    def protocol_batched(self, n: int, n_dishonest: int, seed_base: int, counts: Counts,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The protocol rounds of every instance of ``counts`` (the per-instance
+        tables of sample_check_batched) in one launch (tfg.py:101-125, 166-196,
+        266-306, 337-363): int32 [n_inst, 4 + 5*(n+1)], layout in qba.h."""
+        self._check_n(n)
+        _, w = self.sizes(n)
+        g = n + 1
+        n_inst = counts.P.shape[0] if counts.P.dim() == 2 else -1
+        for t, shape in ((counts.H, (n_inst, w, g, w)), (counts.C, (n_inst, w, g, g)), (counts.P, (n_inst, w))):
+            if t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous() or \
+                    t.device != self.device:
+                raise QbaError("counts must be contiguous int64 [n_inst, ...] tensors of sample_check_batched")
+        words = 4 + 5 * g
+        if out is None:
+            out = torch.empty((n_inst, words), dtype=torch.int32, device=self.device)
+        if out.dtype != torch.int32 or tuple(out.shape) != (n_inst, words) or not out.is_contiguous() or \
+                out.device != self.device:
+            raise QbaError(f"out must be a contiguous int32 [{n_inst}, {words}] device tensor")
+        call("qba_protocol_batched", self.ctx, n, n_dishonest, seed_base, n_inst, _ptr(counts.H), _ptr(counts.C),
+             _ptr(counts.P), _ptr(out), self.stream())
+        return out
+
     # -- (A5-A8) count mode -------------------------------------------------------
     def check_counts(self, lists: torch.Tensor, n: int, count: int,
                      counts: Optional[Counts] = None, accumulate: bool = False) -> Counts:

@@ -1,0 +1,205 @@
+"""Monte-Carlo runs of the count-mode protocol: many independent instances,
+their rounds and decisions computed on the device.
+
+The reference answers "how often does agreement succeed at this sizeL with
+this many traitors?" by running tfg.py again and again (its ``Success:``
+line, tfg.py:362-363).  Here the lists of a batch of instances are sampled and
+counted by ``Engine.sample_check_batched`` and their protocol rounds decided
+by ``Engine.protocol_batched`` (qba_protocol_batched, csrc/qba_proto.hip); only
+the small result rows come to the host.
+
+Both sides draw from one counter-based stream (:class:`ProtocolRng`; layout in
+csrc/qba_internal.h), so :func:`run_host` -- the existing CountParty under
+``protocol.run_local`` on that stream -- is the kernel's specification: the
+two agree in every field of every instance.
+
+Result row of one instance (int32, ``out_words(n)`` = 4 + 5*(n+1) words):
+``{success, dishonest-rank bitmask, empty-V_i rank bitmask, status}`` then per
+rank r = 0..n ``{decision (-1 on an empty V_i), V_r bitmask, accept, reject,
+sent}`` (rank 0: zeros; the commander keeps no V).  status bit 0 = mailbox
+overflow (device only), bit 1 = an RNG retry cap was hit; with a nonzero status
+every other field is 0.
+"""
+from __future__ import annotations
+
+from typing import Callable, Dict, Optional
+
+import numpy as np
+
+from . import protocol
+from ._lib import QbaError
+from .countmode import CountParty
+
+MASK64 = (1 << 64) - 1
+CTR_TAG = 0x51424150  # word 3 of every protocol counter; the sampler's is 0 or 1
+RNG_CAP = 64          # words one randint may draw
+ST_MAILBOX, ST_RNG = 1, 2
+
+_M0, _M1 = 0xD2511F53, 0xCD9E8D57
+_W0, _W1 = 0x9E3779B9, 0xBB67AE85
+_U32 = 0xFFFFFFFF
+
+
+def philox4x32(ctr, key: int):
+    """Philox4x32-10 (Salmon et al., SC'11): the 4 output words of counter
+    ``ctr`` under the 64-bit ``key`` taken as (lo, hi)."""
+    c0, c1, c2, c3 = (int(x) & _U32 for x in ctr)
+    k0, k1 = key & _U32, (key >> 32) & _U32
+    for _ in range(10):
+        p0, p1 = _M0 * c0, _M1 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & _U32, (p0 >> 32) ^ c3 ^ k1, p0 & _U32
+        k0, k1 = (k0 + _W0) & _U32, (k1 + _W1) & _U32
+    return c0, c1, c2, c3
+
+
+def out_words(n: int) -> int:
+    return 4 + 5 * (n + 1)
+
+
+class ProtocolRng:
+    """The stream of rank ``rank`` of the instance keyed ``key``: word t is
+    output word t % 4 of Philox4x32-10 with counter {t / 4, rank, 0, CTR_TAG}.
+    Offers exactly what Party calls: ``randint`` and ``choice``."""
+
+    def __init__(self, key: int, rank: int):
+        self.key, self.rank = int(key) & MASK64, int(rank)
+        self.t = 0
+        self.capped = False
+        self._blk, self._words = -1, None
+
+    def word(self) -> int:
+        blk = self.t >> 2
+        if blk != self._blk:
+            self._words = philox4x32((blk, self.rank, 0, CTR_TAG), self.key)
+            self._blk = blk
+        x = self._words[self.t & 3]
+        self.t += 1
+        return x
+
+    def randint(self, k: int) -> int:
+        """Uniform in [0, k), 1 <= k <= 2^16, by Lemire's method: m = x * k,
+        accept m >> 32 when (uint32)m >= 2^32 mod k.  After RNG_CAP rejected
+        words ``capped`` is set and the last candidate returned."""
+        k = int(k)
+        if not 1 <= k <= 1 << 16:
+            raise ValueError("randint(k) needs 1 <= k <= 2^16")
+        thr = (1 << 32) % k
+        r = 0
+        for _ in range(RNG_CAP):
+            m = self.word() * k
+            r = m >> 32
+            if (m & _U32) >= thr:
+                return r
+        self.capped = True
+        return r
+
+    def choice(self, a, m: int, replace: bool = False) -> np.ndarray:
+        """``m`` distinct elements of ``a``: partial Fisher-Yates, a[j] swapped
+        with a[j + randint(len(a) - j)] for j < m; the result is a[:m]."""
+        if replace:
+            raise ValueError("only choice(..., replace=False) is defined")
+        a = np.array(a, copy=True)
+        if not 0 <= m <= len(a):
+            raise ValueError("cannot take more elements than there are")
+        for j in range(m):
+            s = j + self.randint(len(a) - j)
+            a[j], a[s] = a[s], a[j]
+        return a[:m]
+
+
+def _recording(cls, sink: Dict[int, protocol.Party]):
+    class Recorded(cls):
+        def __init__(self, *a, **kw):
+            super().__init__(*a, **kw)
+            sink[self.rank] = self
+    return Recorded
+
+
+def _mask(values) -> int:
+    m = 0
+    for v in values:
+        m |= 1 << int(v)
+    return m
+
+
+def run_host(n: int, sizeL: int, n_dishonest: int, n_inst: int, seed_base: int, engine, lists=None,
+             party_cls=None, rng_factory: Optional[Callable] = None) -> np.ndarray:
+    """The specification of qba_protocol_batched: CountParty under
+    ``protocol.run_local`` (LocalWorld's barrier-epoch delivery: a round's inbox
+    is everything sent in the previous epoch, in (source, sequence) order,
+    drained before any packet is processed) for instance i with list seed
+    ``seed_base + i`` and :class:`ProtocolRng` streams of the same key.
+
+    ``engine`` needs only ``count_tables`` (the GPU Engine or the tests' numpy
+    engine); ``lists`` injects [n_inst, n+1, sizeL] values instead of sampling.
+    ``party_cls`` (a CountParty subclass) and ``rng_factory`` ((key, rank) ->
+    rng) are observation seams for tests.  Returns int32 [n_inst, out_words(n)].
+    """
+    out = np.zeros((n_inst, out_words(n)), np.int32)
+    make = rng_factory or ProtocolRng
+    for i in range(n_inst):
+        key = (int(seed_base) + i) & MASK64
+        parties: Dict[int, protocol.Party] = {}
+        rngs = []
+
+        def factory(_seed, rank, key=key, rngs=rngs):
+            rngs.append(make(key, rank))
+            return rngs[-1]
+
+        run = protocol.run_local(n, sizeL, n_dishonest, engine, lists=None if lists is None else lists[i],
+                                 list_seed=key, party_cls=_recording(party_cls or CountParty, parties),
+                                 rng_factory=factory)
+        status = ST_RNG if any(getattr(r, "capped", False) for r in rngs) else 0
+        row = out[i]
+        row[3] = status
+        if status:
+            continue
+        row[0] = int(run.result["success"])
+        row[1] = _mask(run.result["dishonest"])
+        row[2] = _mask(run.error_ranks)
+        for r in range(1, n + 1):
+            p = parties[r]
+            row[4 + 5 * r:9 + 5 * r] = (run.result["decisions"][r - 1], _mask(p.Vi) if r > 1 else 0,
+                                        p.stats.accept, p.stats.reject, p.stats.sent)
+    return out
+
+
+def summarize(n: int, out: np.ndarray) -> dict:
+    """Totals of result rows [runs, out_words(n)]: runs, successes, rate, the
+    runs with an empty-V_i error, and the histogram of the honest ranks'
+    decisions {value: count} (-1 = empty V_i).  QbaError on a nonzero status."""
+    out = np.asarray(out).reshape(-1, out_words(n))
+    bad = np.nonzero(out[:, 3])[0]
+    if len(bad):
+        raise QbaError(f"{len(bad)} instance(s) ended with a nonzero status "
+                       f"(first: instance {int(bad[0])}, status {int(out[bad[0], 3])})")
+    runs = len(out)
+    ok = int(out[:, 0].sum())
+    dec = out[:, 4 + 5:4 + 5 * (n + 1):5]                                # ranks 1..n
+    honest = ((out[:, 1:2] >> np.arange(1, n + 1)) & 1) == 0
+    vals, cnt = np.unique(dec[honest], return_counts=True)
+    return {"runs": runs, "successes": ok, "rate": ok / runs if runs else 0.0,
+            "empty_vi_runs": int(np.count_nonzero(out[:, 2])),
+            "decisions": {int(v): int(c) for v, c in zip(vals, cnt)}}
+
+
+def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, packed: bool = True,
+        batch: int = 4096) -> dict:
+    """``runs`` independent instances on the device, ``batch`` at a time:
+    sample_check_batched then protocol_batched with key ``seed + offset``; the
+    list buffer is reused across batches and only the result rows are copied
+    to the host.  Returns :func:`summarize` of all rows."""
+    import torch
+    if runs < 0 or batch < 1:
+        raise ValueError("runs >= 0 and batch >= 1")
+    lists, outs = None, []
+    for off in range(0, runs, batch):
+        b = min(batch, runs - off)
+        key = (int(seed) + off) & MASK64
+        buf, counts = engine.sample_check_batched(n, key, b, sizeL, None if lists is None else lists[:b],
+                                                  packed=packed)
+        if lists is None:
+            lists = buf
+        outs.append(engine.protocol_batched(n, n_dishonest, key, counts))
+    rows = torch.cat(outs).cpu().numpy() if outs else np.zeros((0, out_words(n)), np.int32)
+    return summarize(n, rows)

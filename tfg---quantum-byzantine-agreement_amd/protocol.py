@@ -651,11 +651,14 @@ def _rank_rng(seed: int, rank: int) -> np.random.RandomState:
 def run_local(n_parties: int, sizeL: int, nDishonest: int, engine, seed: int = 0,
               lists: Optional[np.ndarray] = None, log: Optional[Callable] = None,
               list_seed: Optional[int] = None, timeout: float = 120.0,
-              party_cls=None, party_kwargs: Optional[dict] = None) -> LocalRun:
+              party_cls=None, party_kwargs: Optional[dict] = None,
+              rng_factory: Optional[Callable] = None) -> LocalRun:
     """Run all n+1 ranks in-process on a LocalWorld.
 
     Rank r draws from ``np.random.RandomState(seed*1000 + r)`` (the fixtures'
-    convention).  A lieutenant whose V_i is empty raises ValueError in
+    convention), or from ``rng_factory(seed*1000 + r, r)`` when one is given
+    (montecarlo.py: the counter-based streams the device kernel restates).
+    A lieutenant whose V_i is empty raises ValueError in
     decide_order exactly like the reference; here it is recorded in
     ``error``/``error_ranks`` and the run completes with decision -1.
     """
@@ -664,7 +667,7 @@ def run_local(n_parties: int, sizeL: int, nDishonest: int, engine, seed: int = 0
     parties: List[Optional[Party]] = [None] * (n_parties + 1)
 
     def body(c):
-        rs = _rank_rng(seed * 1000 + c.rank, c.rank)
+        rs = (rng_factory or _rank_rng)(seed * 1000 + c.rank, c.rank)
         p = (party_cls or Party)(c, sizeL, nDishonest, shared, rs, log, lists,
                                  seed if list_seed is None else list_seed, **(party_kwargs or {}))
         p.tolerate_empty_vi = True

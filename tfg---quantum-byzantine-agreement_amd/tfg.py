@@ -51,6 +51,10 @@ def _args(argv):
     ap.add_argument("--rounds", choices=["reference", "epoch"], default="reference",
                     help="reference: tfg.py's own (racy) rounds; epoch: barrier-epoch delivery")
     ap.add_argument("--seed", type=int, default=None, help="rank RNG seed and list seed")
+    ap.add_argument("--runs", type=int, default=None,
+                    help="in-process: this many independent count-mode instances, lists, rounds and decisions "
+                         "on the device (montecarlo.run); prints runs, successes and the success rate")
+    ap.add_argument("--batch", type=int, default=4096, help="instances per device batch of --runs")
     ap.add_argument("--quiet", action="store_true", help="print only the outcome")
     ap.add_argument("--timing", action="store_true", help="print the wall time of the run")
     ap.add_argument("--wire", action="store_true",
@@ -168,6 +172,20 @@ def _torchrun(a, size_l, verbose, log) -> int:
     return 1 if run.error else 0
 
 
+def _montecarlo(a, eng, size_l) -> int:
+    """--runs R: R independent count-mode instances decided on the device
+    (montecarlo.run); one summary line."""
+    from . import montecarlo
+    seed = secrets.randbits(62) if a.seed is None else a.seed
+    t0 = time.perf_counter()
+    s = montecarlo.run(a.parties, size_l, a.nDishonest, a.runs, seed, eng, batch=a.batch)
+    print(f"Runs: {s['runs']} Successes: {s['successes']} Rate: {s['rate']:.6f} "
+          f"(n={a.parties}, sizeL={size_l}, dishonest={a.nDishonest}, empty-V_i runs={s['empty_vi_runs']})")
+    if a.timing:
+        print(f"wall {time.perf_counter() - t0:.3f} s ({a.runs} instances on the device)")
+    return 0
+
+
 def main(argv=None) -> int:
     a = _args(sys.argv[1:] if argv is None else argv)
     size_l = int(a.sizeL)
@@ -180,6 +198,8 @@ def main(argv=None) -> int:
         return _torchrun(a, size_l, verbose, log)
     from .engine import Engine
     eng = Engine(0)
+    if a.runs is not None:
+        return _montecarlo(a, eng, size_l)
     seed = secrets.randbits(20) if a.seed is None else a.seed
     list_seed = secrets.randbits(62) if a.seed is None else a.seed
     party_cls = countmode.CountParty if a.mode == "count" else protocol.Party

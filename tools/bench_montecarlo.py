@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""Where the time of BASELINE configs[3] as a Monte-Carlo run goes: 4096
+instances x n = 7 x sizeL = 1e5, 2 dishonest, on one GPU.
+
+  (a) sample_check_batched (nibble rows): lists + count tables of all instances
+  (b) protocol_batched: every instance's rounds, decisions and success flag
+  (c) the only route to the same answers without (b): montecarlo.run_host
+      (CountParty under run_local, one instance at a time, on the GPU engine)
+      over --host-instances instances, scaled to 4096 -- EXTRAPOLATED.
+
+(a) and (b) are device-event times of single calls on warm code: median, min
+and max over --repeats launches after --warmup launches.  (c) is host wall
+time around runs that end in device synchronisation (each reads its tables
+back).  Prints one JSON line; --out also writes it to a file.  No GPU: fails.
+"""
+import argparse
+import importlib
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+PKG = "tfg---quantum-byzantine-agreement_amd"
+
+
+def _events(fn, warmup, repeats):
+    import torch
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "launches": repeats}
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--parties", type=int, default=7)
+    ap.add_argument("--sizeL", type=int, default=100_000)
+    ap.add_argument("--dishonest", type=int, default=2)
+    ap.add_argument("--instances", type=int, default=4096)
+    ap.add_argument("--host-instances", type=int, default=64)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=50)
+    ap.add_argument("--seed", type=int, default=0x5EED)
+    ap.add_argument("--out", type=Path, default=None)
+    a = ap.parse_args(argv)
+
+    import torch
+    eng = importlib.import_module(f"{PKG}.engine").Engine(0)
+    mc = importlib.import_module(f"{PKG}.montecarlo")
+    n, nd, inst = a.parties, a.dishonest, a.instances
+    lists, counts = eng.sample_check_batched(n, a.seed, inst, a.sizeL, packed=True)
+    out = eng.protocol_batched(n, nd, a.seed, counts)
+    torch.cuda.synchronize()
+
+    res = {"config": {"n": n, "sizeL": a.sizeL, "dishonest": nd, "instances": inst, "seed": a.seed,
+                      "device": torch.cuda.get_device_name(0)}}
+    res["a_sample_check_batched_packed"] = _events(
+        lambda: eng.sample_check_batched(n, a.seed, inst, a.sizeL, lists, packed=True), a.warmup, a.repeats)
+    res["b_protocol_batched"] = _events(lambda: eng.protocol_batched(n, nd, a.seed, counts, out), a.warmup,
+                                        a.repeats)
+    table_bytes = 8 * inst * sum(int(t[0].numel()) for t in (counts.H, counts.C, counts.P))
+    res["b_protocol_batched"]["table_bytes_read"] = table_bytes
+    res["b_protocol_batched"]["table_GBps_at_median"] = table_bytes / res["b_protocol_batched"]["median_ms"] / 1e6
+    summary = mc.summarize(n, out.cpu().numpy())
+    res["result"] = {k: summary[k] for k in ("runs", "successes", "rate", "empty_vi_runs")}
+
+    k = a.host_instances
+    mc.run_host(n, a.sizeL, nd, 2, a.seed, eng)  # warm
+    t0 = time.perf_counter()
+    host = mc.run_host(n, a.sizeL, nd, k, a.seed, eng)
+    wall = time.perf_counter() - t0
+    res["c_run_host_gpu_engine"] = {"instances": k, "wall_s": wall, "per_instance_ms": 1e3 * wall / k,
+                                    "extrapolated_to_instances": inst,
+                                    "extrapolated_s": wall / k * inst, "extrapolated": True,
+                                    "rows_equal_kernel": bool((host == out[:k].cpu().numpy()).all())}
+    res["b_below_a"] = res["b_protocol_batched"]["median_ms"] < res["a_sample_check_batched_packed"]["median_ms"]
+    line = json.dumps(res)
+    print(line)
+    if a.out is not None:
+        a.out.parent.mkdir(parents=True, exist_ok=True)
+        a.out.write_text(line + "\n")
+    eng.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
