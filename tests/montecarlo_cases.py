@@ -8,6 +8,9 @@ The C twin samples n <= 11 only, so the n = 15 host reference takes injected
 lists: on the GPU the device-sampled lists themselves, on the CPU lists of the
 same law drawn with numpy (tfg_oracle.closed_form_lists).
 """
+import json
+from pathlib import Path
+
 import numpy as np
 
 import tfg_oracle as orc
@@ -26,6 +29,32 @@ IDS = [f"n{n}-d{d}-L{s}" for n, d, s in CASES]
 # Cond3 collisions; the source of rejected commander packets and empty V_i),
 # its lists replicated for INJECT_KEYS protocol keys from INJECT_BASE
 INJECT_BASE, INJECT_KEYS = 7000, 16
+
+
+# the hostile sets and the sweep over every n (tests/golden/hostile_lists.npz,
+# written by tests/golden/gen_hostile_lists.py, which describes the mutation
+# families): lists with duplicated rows, many traitors.  They reach what honest
+# lists cannot: descriptor canonicalisation (rep != g), L of 6 and more
+# descriptors, rounds 5 and above, several packets per mailbox.
+_HOSTILE = np.load(Path(__file__).resolve().parent / "golden" / "hostile_lists.npz")
+_META = json.loads(str(_HOSTILE["meta"]))
+HOSTILE = _META["hostile"]   # dicts: name, n, nDishonest, sizeL, family, base, keys, rows[, u | src]
+SWEEP = _META["sweep"]       # dicts: name, n, nDishonest, sizeL, base, keys
+HOSTILE_IDS = [c["name"] for c in HOSTILE]
+SWEEP_IDS = [c["name"] for c in SWEEP]
+DUP_FAMILIES = ("dup_all", "dup_u", "dup3", "dup_cmd")
+
+
+def hostile_lists(case):
+    """[keys, n+1, sizeL] uint8 of a HOSTILE or SWEEP entry (read-only): a
+    hostile set's one list under each of its keys, a sweep entry's own lists."""
+    li = _HOSTILE[case["name"]]
+    if li.ndim == 2:
+        li = np.broadcast_to(li, (case["keys"],) + li.shape)
+    assert li.shape == (case["keys"], case["n"] + 1, case["sizeL"]) and li.dtype == np.uint8
+    li = li.view()
+    li.setflags(write=False)
+    return li
 
 
 def cpu_lists(n, sizeL, seed_base, n_inst):

@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, sub
-from montecarlo_cases import CASES, IDS, INJECT_BASE, INJECT_KEYS
+from montecarlo_cases import (CASES, HOSTILE, HOSTILE_IDS, IDS, INJECT_BASE, INJECT_KEYS, SWEEP, SWEEP_IDS,
+                              hostile_lists)
 from oracle_engine import OracleEngine
 
 pytestmark = pytest.mark.gpu
@@ -77,6 +78,99 @@ def test_injected_lists_equal_host_reference(engine, case):
     want = mc.run_host(n, sizeL, nd, INJECT_KEYS, INJECT_BASE, OracleEngine(),
                        lists=np.broadcast_to(li, (INJECT_KEYS,) + li.shape))
     _assert_rows(got.cpu().numpy(), want, n)
+
+
+@pytest.fixture(scope="module")
+def hostile(engine):
+    """Per hostile set or sweep entry: the device tables under its keys, the
+    kernel's rows and the host reference's rows, computed once."""
+    import torch
+    mc, Counts = sub("montecarlo"), sub("engine").Counts
+    memo = {}
+
+    def get(case):
+        if case["name"] not in memo:
+            n, nd, sizeL, keys = case["n"], case["nDishonest"], case["sizeL"], case["keys"]
+            li = hostile_lists(case)
+            _, w = engine.sizes(n)
+            g = n + 1
+            h, c = w * g * w, w * g * g
+            # a hostile set: one list, its tables replicated under the keys; a sweep entry: a list per key
+            distinct = 1 if li.strides[0] == 0 else keys
+            flat = torch.stack([engine.count_tables(n, sizeL, lists=np.array(li[i]), device_out=True)
+                                for i in range(distinct)]).expand(keys, -1)
+            counts = Counts(flat[:, :h].reshape(keys, w, g, w).contiguous(),
+                            flat[:, h:h + c].reshape(keys, w, g, g).contiguous(), flat[:, h + c:].contiguous())
+            got = engine.protocol_batched(n, nd, case["base"], counts).cpu().numpy()
+            want = mc.run_host(n, sizeL, nd, keys, case["base"], OracleEngine(), lists=li)
+            for a in (got, want):
+                a.setflags(write=False)
+            memo[case["name"]] = (counts, got, want)
+        return memo[case["name"]]
+    return get
+
+
+@pytest.mark.parametrize("case", HOSTILE + SWEEP, ids=HOSTILE_IDS + SWEEP_IDS)
+def test_hostile_lists_equal_host_reference(hostile, case):
+    """Lists with duplicated rows and many traitors (canonicalised descriptors,
+    rep in {0, 1}, L of 8 descriptors, round 7, 6 packets in one mailbox, V_i
+    of 10 values: test_montecarlo.test_hostile_sets_reach_every_path), and
+    honest lists at every n from 1 to 15."""
+    _, got, want = hostile(case)
+    _assert_rows(got, want, case["n"])
+
+
+WIDE = [c for c in HOSTILE if c["name"] in ("n3-d2-L30-dup_u", "n15-d14-L96-dup3")]  # w = 4 and w = 16
+
+
+@pytest.mark.parametrize("shift", [32, 31])
+@pytest.mark.parametrize("case", WIDE, ids=[c["name"] for c in WIDE])
+def test_tables_are_read_as_64_bit_values(engine, hostile, case, shift):
+    """The specification consults only != 0, == 0 and C == P, so tables scaled
+    by 2^32 (low words all zero) or 2^31 (low word = the count's parity, in the
+    sign bit) give the same rows."""
+    Counts = sub("engine").Counts
+    counts, got, want = hostile(case)
+    big = Counts(counts.H * (1 << shift), counts.C * (1 << shift), counts.P * (1 << shift))
+    assert int(big.P.max()) >= 1 << shift and int(big.C.max()) >= 1 << shift and int(big.H.max()) >= 1 << shift
+    rows = engine.protocol_batched(case["n"], case["nDishonest"], case["base"], big).cpu().numpy()
+    assert np.array_equal(rows, got)
+    _assert_rows(rows, want, case["n"])
+
+
+def test_out_is_overwritten_in_every_word_and_checked(engine, hostile):
+    import torch
+    QbaError, Counts = sub("_lib").QbaError, sub("engine").Counts
+    case = next(c for c in HOSTILE if c["name"] == "n7-d4-L60-dup_all")
+    n, nd, base, keys = case["n"], case["nDishonest"], case["base"], case["keys"]
+    counts, got, _ = hostile(case)
+    words = 4 + 5 * (n + 1)
+    fill = 0x7F7F7F7F
+    out = torch.full((keys, words), fill, dtype=torch.int32, device=engine.device)
+    ret = engine.protocol_batched(n, nd, base, counts, out=out)
+    assert ret.data_ptr() == out.data_ptr()
+    rows = out.cpu().numpy()
+    assert not np.any(rows == fill) and np.array_equal(rows, got)
+
+    def run(c=counts, o=None):
+        return engine.protocol_batched(n, nd, base, c, out=o)
+
+    new = lambda *shape, dtype=torch.int32, device=engine.device: \
+        torch.zeros(shape, dtype=dtype, device=device)  # noqa: E731
+    for bad in (new(keys, words, dtype=torch.int64), new(keys, words, dtype=torch.float32),
+                new(keys + 1, words), new(keys, words + 1), new(keys * words),
+                new(keys, words, device="cpu"), new(keys, 2 * words)[:, ::2], new(words, keys).t()):
+        with pytest.raises(QbaError):
+            run(o=bad)
+    H, C, P = counts.H, counts.C, counts.P
+    assert H.transpose(1, 3).shape == H.shape and not H.transpose(1, 3).is_contiguous()
+    for bad in (Counts(H.transpose(1, 3), C, P), Counts(H, C.transpose(2, 3), P),
+                Counts(H, C, torch.stack([P, P], 2)[:, :, 0]),
+                Counts(H.to(torch.int32), C, P), Counts(H, C.cpu(), P), Counts(H, C, P[:-1]),
+                Counts(H[:, :, :, :-1].contiguous(), C, P)):
+        with pytest.raises(QbaError):
+            run(c=bad)
+    assert np.array_equal(run().cpu().numpy(), got)  # and the engine still works
 
 
 def test_streams_split_batches_and_single_instance(engine, sampled):

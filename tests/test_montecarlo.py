@@ -1,6 +1,7 @@
 """montecarlo.py on the CPU: the counter-based protocol RNG, the host
 reference run_host (CountParty on that RNG), what the GPU tests' parameter
 sets reach, and the C ABI of qba_protocol_batched without a device."""
+import itertools
 import json
 from pathlib import Path
 
@@ -8,13 +9,16 @@ import numpy as np
 import pytest
 
 import oracle_lib
+import tfg_oracle as orc
 from conftest import GOLDEN, sub
 from kd_util import kernel_descriptors
-from montecarlo_cases import CASES, INJECT_BASE, INJECT_KEYS, cpu_lists
+from montecarlo_cases import (CASES, DUP_FAMILIES, HOSTILE, HOSTILE_IDS, INJECT_BASE, INJECT_KEYS, cpu_lists,
+                              hostile_lists)
 from oracle_engine import OracleEngine
 
 mc = sub("montecarlo")
 countmode = sub("countmode")
+protocol = sub("protocol")
 
 
 # ---------------------------------------------------------------------------
@@ -179,6 +183,162 @@ def test_parameter_sets_reach_every_path():
     assert seen_all["actions"] == {0, 1, 2, 3}, seen_all
     for what in ("fail", "empty_vi", "dis_commander", "late_accept", "reject", "empty_desc"):
         assert seen_all[what] > 0, (what, seen_all)
+
+
+# ---------------------------------------------------------------------------
+# hostile sets: duplicated rows, many traitors (montecarlo_cases.HOSTILE)
+# ---------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def hostile_rows():
+    """run_host's rows (CountParty) per hostile set, computed once, read-only."""
+    memo = {}
+
+    def get(case):
+        if case["name"] not in memo:
+            rows = mc.run_host(case["n"], case["sizeL"], case["nDishonest"], case["keys"], case["base"],
+                               OracleEngine(), lists=hostile_lists(case))
+            rows.setflags(write=False)
+            memo[case["name"]] = rows
+        return memo[case["name"]]
+    return get
+
+
+@pytest.mark.parametrize("case", HOSTILE, ids=HOSTILE_IDS)
+def test_hostile_lists_carry_their_mutation(case):
+    """The fixture's lists against its own description, in terms of the count
+    tables: which C[u][g][h] equal P[u], and for `near` P[u] - 1."""
+    n, fam, rows = case["n"], case["family"], case["rows"]
+    _, C, P = orc.counts(hostile_lists(case)[0], n)
+    full = {(u, g, h) for u in np.nonzero(P)[0] for g in range(n + 1) for h in range(g) if C[u, g, h] == P[u]}
+    us = [int(u) for u in np.nonzero(P)[0]]
+    if fam in ("dup_all", "dup3"):
+        want = {(u, g, h) for u in us for g in rows for h in rows if h < g}
+    elif fam == "dup_u":
+        want = {(case["u"], rows[1], rows[0])}
+    elif fam == "dup_cmd":
+        want = {(u, rows[0], case["src"]) for u in us}
+    else:
+        u, (g, h) = case["u"], rows
+        want = set()
+        assert P[u] >= 2 and C[u, g, h] == P[u] - 1
+    assert full == want and len(us) > 0
+    assert "u" not in case or P[case["u"]] > 0
+
+
+class SortedTupleParty(protocol.Party):
+    """The exact-mode party on real tuples, gathered in ascending index order
+    (count mode's canonical order): Python's own set of tuples de-duplicates,
+    the oracle's `consistent` decides."""
+
+    def own_tuple(self, P):
+        return protocol.make_tuple(self.engine.gather(self.li, np.sort(protocol._wire(P))))
+
+
+@pytest.mark.parametrize("case", HOSTILE, ids=HOSTILE_IDS)
+def test_count_mode_equals_sorted_tuples_on_hostile_lists(hostile_rows, case):
+    """CountParty's descriptor algebra (rep = min h with C[u][g][h] == P[u] for
+    equal tuples, Cond1-3 from the counts) against real tuples: every field of
+    every row.  The unsorted protocol.Party does differ on these lists (each
+    rank gathers in its own set-iteration order, so equal rows need not give
+    equal tuples: V_i, accept and reject counts differ on 15 of the 35 sets,
+    and on other lists of these families a success flag was seen to flip):
+    count mode is defined in canonical order, so that is by design and not
+    asserted."""
+    got = mc.run_host(case["n"], case["sizeL"], case["nDishonest"], case["keys"], case["base"], OracleEngine(),
+                      lists=hostile_lists(case), party_cls=SortedTupleParty)
+    want = hostile_rows(case)
+    assert got.shape == want.shape
+    if not np.array_equal(got, want):
+        i = int(np.argwhere(got != want)[0][0])
+        raise AssertionError(f"instance {i}:\ntuples {got[i].tolist()}\ncounts {want[i].tolist()}")
+
+
+class _Reach:
+    def __init__(self):
+        self.desc = set()    # (u, g, rep) of every non-EMPTY own descriptor
+        self.cond3 = set()   # (u, a, b): reps of one L rejected by Cond3 alone, C[u][a][b] != 0
+        self.max_len = 0     # descriptors of the longest accepted L
+        self.max_round = 0   # the latest round in which a packet was accepted
+        self.max_box = 0     # most packets of one (source, destination, round)
+
+
+def _reach_party(seen):
+    class Reach(countmode.CountParty):
+        _rnd = 0
+
+        def __init__(self, *a, **kw):
+            super().__init__(*a, **kw)
+            self._box = {}
+
+        def lieu_receive(self, P, v, L, rnd, pre=None):
+            self._rnd = rnd
+            return super().lieu_receive(P, v, L, rnd, pre)
+
+        def own_tuple(self, P):
+            d = super().own_tuple(P)
+            if d != countmode.EMPTY:
+                seen.desc.add((d[0], self.rank, d[1]))
+            return d
+
+        def check(self, v, L):
+            ok = super().check(v, L)
+            if ok:
+                seen.max_len = max(seen.max_len, len(L))
+                seen.max_round = max(seen.max_round, self._rnd)
+                return ok
+            t, descs = self.tables, sorted(d for d in L if d != countmode.EMPTY)
+            if len(descs) == len(L) and not any(t.H[u, g, int(v)] for u, g in descs):  # Cond1 and Cond2 hold
+                seen.cond3 |= {(a[0], a[1], b[1]) for a, b in itertools.combinations(descs, 2)
+                               if t.C[a[0], a[1], b[1]] != 0}
+            return ok
+
+        def send(self, dest, P, v, L):
+            k = (dest, self._rnd)
+            self._box[k] = self._box.get(k, 0) + 1
+            seen.max_box = max(seen.max_box, self._box[k])
+            super().send(dest, P, v, L)
+
+    return Reach
+
+
+def test_hostile_sets_reach_every_path(hostile_rows):
+    """What the hostile sets add to test_parameter_sets_reach_every_path, on
+    the host reference alone: canonicalised descriptors in every duplicate
+    family (rep in {0, 1} too), a `near` pair that collides in Cond3 and does
+    not canonicalise, L of >= 6 descriptors, acceptance in round >= 5, >= 3
+    packets in one (source, destination, round) mailbox, V_i of >= 5 values,
+    failed runs, empty V_i, and status 0 throughout."""
+    got = dict(rep_ne_g={f: 0 for f in DUP_FAMILIES}, rep_01=0, near_cond3=0, max_len=0, max_round=0, max_box=0,
+               max_vi=0, fail=0, empty_vi=0, runs=0)
+    for case in HOSTILE:
+        n, fam = case["n"], case["family"]
+        seen = _Reach()
+        out = mc.run_host(n, case["sizeL"], case["nDishonest"], case["keys"], case["base"], OracleEngine(),
+                          lists=hostile_lists(case), party_cls=_reach_party(seen))
+        assert np.array_equal(out, hostile_rows(case)), "the seam changes nothing"
+        assert np.all(out[:, 3] == 0), case["name"]
+        moved = {(u, g, rep) for u, g, rep in seen.desc if rep != g}
+        if fam == "near":
+            u, (g, h) = case["u"], case["rows"]
+            assert not moved, (case["name"], moved)  # one entry apart: nothing canonicalises
+            got["near_cond3"] += (u, g, h) in seen.cond3
+        else:
+            got["rep_ne_g"][fam] += len(moved)
+            # only the duplicated rows move, and to the smallest equal row
+            lo = case["src"] if fam == "dup_cmd" else case["rows"][0]
+            assert all(g in case["rows"] and rep == lo for _, g, rep in moved), (case["name"], moved)
+        got["rep_01"] += sum(1 for _, _, rep in moved if rep < 2)
+        for what in ("max_len", "max_round", "max_box"):
+            got[what] = max(got[what], getattr(seen, what))
+        got["max_vi"] = max(got["max_vi"], max(bin(int(x)).count("1") for x in out[:, 5::5].ravel()))
+        got["fail"] += int(np.sum(out[:, 0] == 0))
+        got["empty_vi"] += int(np.count_nonzero(out[:, 2]))
+        got["runs"] += len(out)
+    print(got)
+    assert all(c > 0 for c in got["rep_ne_g"].values()), got
+    assert got["rep_01"] > 0 and got["near_cond3"] > 0, got
+    assert got["max_len"] >= 6 and got["max_round"] >= 5 and got["max_box"] >= 3 and got["max_vi"] >= 5, got
+    assert got["fail"] > 0 and got["empty_vi"] > 0, got
 
 
 # ---------------------------------------------------------------------------
