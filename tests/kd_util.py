@@ -56,14 +56,12 @@ def _descriptors(elf: bytes) -> dict:
     return out
 
 
-def kernel_descriptors(lib: Path) -> dict:
-    """{mangled kernel name: {"lds", "scratch", "kernarg", "vgprs"}} over
-    every gfx950 code object in `lib`."""
+def code_objects(lib: Path):
+    """The gfx950 code objects (ELF images) of `lib`'s offload bundles, in link order."""
     data = Path(lib).read_bytes()
     secs = _sections(data)
     fat = next(s for s in secs if s["name"] == ".hip_fatbin")
     fb = data[fat["off"]:fat["off"] + fat["size"]]
-    out = {}
     pos = 0
     while (i := fb.find(MAGIC, pos)) >= 0:
         n = struct.unpack_from("<Q", fb, i + 24)[0]
@@ -74,6 +72,14 @@ def kernel_descriptors(lib: Path) -> dict:
             tid = fb[p:p + tl].decode()
             p += tl
             if tid == TARGET and es:
-                out.update(_descriptors(fb[i + eo:i + eo + es]))
+                yield fb[i + eo:i + eo + es]
         pos = i + len(MAGIC)
+
+
+def kernel_descriptors(lib: Path) -> dict:
+    """{mangled kernel name: {"lds", "scratch", "kernarg", "vgprs"}} over
+    every gfx950 code object in `lib`."""
+    out = {}
+    for elf in code_objects(lib):
+        out.update(_descriptors(elf))
     return out

@@ -707,3 +707,91 @@ def test_invalid_arguments_leave_context_usable(engine):
     assert np.array_equal(got[:, :count].cpu().numpy(), ref)
     H, C, P, _ = oracle_lib.counts(ref, n)
     assert np.array_equal(c.numpy()[0], H)
+
+
+# -- the launchers' dispatch matrix (csrc/qba_lists_launch.h) ---------------------
+MATRIX_COUNT, MATRIX_FIRST = 8197, 7  # 1,024 wide units, one whole remaining quad and one partial quad
+MATRIX_SAMPLERS = ["closed3", "closed11", "closed11_pair_bins", "tables12", "general3"]
+
+
+def _general_pair(n):
+    """The circuit pair of test_general_program_path (general alias-table sampler)."""
+    resource = sub("resource")
+    nq = resource.n_qubits(n)
+    notq = resource.Gate((n + 1) * nq)
+    for qb in range(nq, 3 * nq):
+        notq.add_operation("H", targets=qb)
+    for j in range(nq):
+        notq.add_operation("X", targets=j, controls=nq + j)
+        notq.add_operation("X", targets=3 * nq + j, controls=2 * nq + j)
+    return notq, resource.qCorrelated(n, nq, perm=[1, 2, 3])
+
+
+@pytest.fixture(scope="module")
+def matrix(engine):
+    """sampler -> (engine, n, oracle rows, oracle (H, C, P)), computed once.
+    Pair bins are forced (pb_min = 0) and the general program compiled on a
+    fresh Engine, so the session's engine keeps the shipped selection."""
+    forced = sub("engine").Engine(0).set_test_knobs(pb_min=0)
+    out = {}
+    for name, eng, n, flags in [("closed3", engine, 3, (True, True)), ("closed11", engine, 11, (True, True)),
+                                ("closed11_pair_bins", forced, 11, (True, True)),
+                                ("tables12", engine, 12, (False, True)), ("general3", forced, 3, (False, False))]:
+        info = eng.compile(n, *_general_pair(n)) if name == "general3" else eng.prepare(n)
+        assert (info["closed"], info["canonical"]) == flags, name
+        ref = oracle_lib.sample(n, 0xD15 + n, MATRIX_FIRST, MATRIX_COUNT, info["notq"], info["q"], info["closed"])
+        H, C, P, bad = oracle_lib.counts(ref, n)
+        assert bad == 0
+        out[name] = (eng, n, ref, (H, C, P))
+    yield out
+    forced.close()
+
+
+# Cells the API cannot express are left out: nibble rows off their 4-byte
+# vector alignment (every entry point requires base and stride 4-byte aligned),
+# and check_counts on the general sampler (it samples nothing: the same kernel
+# as on any other program).  Pair bins exist at n = 11 only.
+MATRIX_CELLS = [(s, nib, off, call) for s in MATRIX_SAMPLERS for nib in (False, True) for off in (0, 4)
+                for call in ("sample", "sample_check", "sample_check_deferred", "check_counts")
+                if not (nib and off) and not (s == "general3" and call == "check_counts")]
+
+
+@pytest.mark.parametrize("sampler,nibbles,offset,call", MATRIX_CELLS,
+                         ids=[f"{s}-{'nibbles' if nib else 'bytes'}-{'unaligned' if off else 'aligned'}-{call}"
+                              for s, nib, off, call in MATRIX_CELLS])
+def test_launch_dispatch_matrix(matrix, sampler, nibbles, offset, call):
+    """Every branch of the launchers' kernel picker, LDS sizing and grid sizing
+    once, at a size where a wrong (QPT, PK), LDS size or grid shows in the
+    bytes: rows bit-exact and H, C, P equal to the C twin's, and no byte
+    outside [0, count) of a padded buffer written (a nibble row's missing last
+    entry is 0)."""
+    eng, n, ref, (H, C, P) = matrix[sampler]
+    count, first, seed = MATRIX_COUNT, MATRIX_FIRST, 0xD15 + n
+    nb = (count + 1) // 2 if nibbles else count
+    ld = (nb + 63) // 64 * 64 + 64 + offset
+    buf = torch.full((n + 1, ld), 0xA5, dtype=torch.uint8, device=eng.device)
+    view = buf[:, offset:]
+    assert view.data_ptr() % 8 == offset and view.stride(0) % 8 == offset  # offset 4: the one-quad kernels
+    counts = None
+    if call == "sample":
+        (eng.sample_packed if nibbles else eng.sample)(n, seed, first, count, view)
+    elif call == "check_counts":
+        (eng.sample_packed if nibbles else eng.sample)(n, seed, first, count, view)
+        counts = (eng.check_counts_packed if nibbles else eng.check_counts)(view, n, count)
+    else:
+        deferred = call == "sample_check_deferred"
+        _, counts = (eng.sample_check_packed if nibbles else eng.sample_check)(n, seed, first, count, view,
+                                                                               deferred=deferred)
+        if deferred:
+            eng.flush_deferred()
+    torch.cuda.synchronize()
+    host = buf.cpu().numpy()
+    rows = host[:, offset:offset + nb]
+    got = sub("engine").unpack_nibbles(rows, count) if nibbles else rows
+    assert np.array_equal(got, ref)
+    if nibbles and count % 2:
+        assert not (rows[:, -1] >> 4).any()  # the missing entry's nibble
+    assert (host[:, :offset] == 0xA5).all() and (host[:, offset + nb:] == 0xA5).all()  # nothing written outside
+    if counts is not None:
+        gH, gC, gP = counts.numpy()
+        assert np.array_equal(gH, H) and np.array_equal(gC, C) and np.array_equal(gP, P)

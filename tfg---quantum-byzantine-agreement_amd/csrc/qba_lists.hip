@@ -1,5 +1,7 @@
 // qba_lists.hip -- C ABI of the list kernels: argument checks, 2^31-entry
 // launch chunks and dispatch to the per-n instantiations (qba_lists_inst.hip).
+#include <type_traits>
+
 #include "qba_lists.h"
 
 // Experiment builds only (tools/exp): restrict instantiation to one n.
@@ -46,6 +48,19 @@ static int need_program(qba_ctx *ctx, int n, const char *who) {
   return QBA_OK;
 }
 
+// f(std::integral_constant<int, n>()) for the n of a call: the per-n
+// instantiations (an experiment build, QBA_ONLY_N, has those of one n only)
+template <int K = 1, class F>
+static int with_n(int n, const F &f) {
+  if constexpr (K > QBA_MAX_PARTIES) {
+    return qba_fail(QBA_EUNSUPPORTED, "n_parties must be in [1, 15]");
+  } else {
+    if (n != K) return with_n<K + 1>(n, f);
+    if constexpr (QBA_ONLY_N == 0 || K == QBA_ONLY_N) return f(std::integral_constant<int, K>());
+    return qba_fail(QBA_EUNSUPPORTED, "experiment build");
+  }
+}
+
 static int batched(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst, uint64_t count, uint8_t *lists,
                    uint64_t ld, uint64_t inst_stride, int64_t *H, int64_t *C, int64_t *P, qba_stream stream,
                    bool packed, const char *who) {
@@ -59,49 +74,21 @@ static int batched(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst, uint
   if ((rc = need_program(ctx, n, who))) return rc;
   QbaBatch B{n, (const QbaProgramSet *)ctx->prog_dev[n], seed_base, n_inst, count, lists, ld,
              inst_stride, H, C, P, (hipStream_t)stream, packed ? 1 : 0};
-  switch (n) {
-#define QBA_CASE(k)                                                                     \
-  case k:                                                                               \
-    if constexpr (QBA_ONLY_N == 0 || k == QBA_ONLY_N) return qba_launch_batched<k>(ctx, B); \
-    return qba_fail(QBA_EUNSUPPORTED, "experiment build");
-    QBA_CASE(1) QBA_CASE(2) QBA_CASE(3) QBA_CASE(4) QBA_CASE(5) QBA_CASE(6) QBA_CASE(7)
-    QBA_CASE(8) QBA_CASE(9) QBA_CASE(10) QBA_CASE(11) QBA_CASE(12) QBA_CASE(13) QBA_CASE(14)
-    QBA_CASE(15)
-#undef QBA_CASE
-    default:
-      return qba_fail(QBA_EUNSUPPORTED, "n_parties must be in [1, 15]");
-  }
+  return with_n(n, [&](auto k) { return qba_launch_batched<decltype(k)::value>(ctx, B); });
 }
 
-extern "C" int qba_sample_check_batched(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst,
-                                        uint64_t count, uint8_t *lists, uint64_t ld,
-                                        uint64_t inst_stride, int64_t *H, int64_t *C, int64_t *P,
-                                        qba_stream stream) {
+extern "C" int qba_sample_check_batched(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst, uint64_t count,
+                                        uint8_t *lists, uint64_t ld, uint64_t inst_stride, int64_t *H, int64_t *C,
+                                        int64_t *P, qba_stream stream) {
   return batched(ctx, n, seed_base, n_inst, count, lists, ld, inst_stride, H, C, P, stream, false,
                  "qba_sample_check_batched");
 }
 
-extern "C" int qba_sample_check_batched_packed(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst,
-                                               uint64_t count, uint8_t *packed, uint64_t ld,
-                                               uint64_t inst_stride, int64_t *H, int64_t *C, int64_t *P,
-                                               qba_stream stream) {
+extern "C" int qba_sample_check_batched_packed(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst, uint64_t count,
+                                               uint8_t *packed, uint64_t ld, uint64_t inst_stride, int64_t *H,
+                                               int64_t *C, int64_t *P, qba_stream stream) {
   return batched(ctx, n, seed_base, n_inst, count, packed, ld, inst_stride, H, C, P, stream, true,
                  "qba_sample_check_batched_packed");
-}
-
-static int dispatch_one(qba_ctx *ctx, const QbaLaunch &L) {
-  switch (L.n) {
-#define QBA_CASE(k)                                                                   \
-  case k:                                                                             \
-    if constexpr (QBA_ONLY_N == 0 || k == QBA_ONLY_N) return qba_launch_lists<k>(ctx, L); \
-    return qba_fail(QBA_EUNSUPPORTED, "experiment build");
-    QBA_CASE(1) QBA_CASE(2) QBA_CASE(3) QBA_CASE(4) QBA_CASE(5) QBA_CASE(6) QBA_CASE(7)
-    QBA_CASE(8) QBA_CASE(9) QBA_CASE(10) QBA_CASE(11) QBA_CASE(12) QBA_CASE(13) QBA_CASE(14)
-    QBA_CASE(15)
-#undef QBA_CASE
-    default:
-      return qba_fail(QBA_EUNSUPPORTED, "n_parties must be in [1, 15]");
-  }
 }
 
 // Launches of at most QBA_CHUNK entries (32-bit in-kernel offsets, u32 bins)
@@ -139,7 +126,7 @@ static int dispatch(qba_ctx *ctx, const QbaLaunch &L0) {
     L.lists = at;
     L.accumulate = done ? 1 : L0.accumulate;
     L.stats_accumulate = done ? 1 : 0;
-    rc = dispatch_one(ctx, L);
+    rc = with_n(L.n, [&](auto k) { return qba_launch_lists<decltype(k)::value>(ctx, L); });
     done += L.count;
   } while (!rc && done < L0.count);
   return rc;
@@ -248,107 +235,94 @@ static int zero_counts(qba_ctx *ctx, int n, int64_t *H, int64_t *C, int64_t *P, 
   return QBA_OK;
 }
 
-extern "C" int qba_sample(qba_ctx *ctx, int n, uint64_t seed, uint64_t first, uint64_t count,
-                          uint8_t *lists, uint64_t ld, qba_stream stream) {
-  int rc = check_common(ctx, n, lists, count, ld, "qba_sample");
-  if (rc || count == 0) return rc;
-  if ((rc = need_program(ctx, n, "qba_sample"))) return rc;
-  QbaLaunch L{n, 0, (const QbaProgramSet *)ctx->prog_dev[n], seed, first, count, lists, ld,
-              nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream};
+// The list entry points below: argument checks, the rule for count == 0 (a
+// counting call still zeroes its outputs, or lets a pending reduction that
+// may target them finish) and the launch descriptor.  mode 0: sample, 1:
+// sample + check, 2: check only, which samples nothing and needs no program.
+enum { BYTE_ROWS = 0, NIBBLE_ROWS = 1, DEFER = 2 };
+static int lists_call(const char *who, int mode, int how, qba_ctx *ctx, int n, uint64_t seed, uint64_t first,
+                      uint64_t count, uint8_t *lists, uint64_t ld, int64_t *H, int64_t *C, int64_t *P,
+                      int accumulate, qba_stream stream) {
+  const bool packed = how & NIBBLE_ROWS;
+  const hipStream_t s = (hipStream_t)stream;
+  int rc = check_common(ctx, n, lists, count, ld, who, packed);
+  if (rc) return rc;
+  if (mode != 0) {
+    if (!H || !C || !P) return qba_fail(QBA_EINVAL, std::string(who) + ": H, C and P are required");
+    if (count == 0) return accumulate ? qba_flush_pending(ctx, s) : zero_counts(ctx, n, H, C, P, s);
+  }
+  if (count == 0) return QBA_OK;
+  if (mode != 2 && (rc = need_program(ctx, n, who))) return rc;
+  QbaLaunch L{};
+  L.n = n;
+  L.mode = mode;
+  L.ps = mode != 2 ? (const QbaProgramSet *)ctx->prog_dev[n] : nullptr;
+  L.seed = seed;
+  L.first = first;
+  L.count = count;
+  L.lists = lists;
+  L.ld = ld;
+  L.H = H;
+  L.C = C;
+  L.P = P;
+  L.stats = mode != 0 ? ctx->stats : nullptr;
+  L.accumulate = accumulate;
+  L.stream = s;
+  L.packed = packed ? 1 : 0;
+  L.defer = how & DEFER ? 1 : 0;
   return dispatch(ctx, L);
 }
 
-extern "C" int qba_sample_check(qba_ctx *ctx, int n, uint64_t seed, uint64_t first,
-                                uint64_t count, uint8_t *lists, uint64_t ld, int64_t *H,
+extern "C" int qba_sample(qba_ctx *ctx, int n, uint64_t seed, uint64_t first, uint64_t count, uint8_t *lists,
+                          uint64_t ld, qba_stream stream) {
+  return lists_call("qba_sample", 0, BYTE_ROWS, ctx, n, seed, first, count, lists, ld, nullptr, nullptr, nullptr, 0,
+                    stream);
+}
+
+extern "C" int qba_sample_check(qba_ctx *ctx, int n, uint64_t seed, uint64_t first, uint64_t count, uint8_t *lists,
+                                uint64_t ld, int64_t *H, int64_t *C, int64_t *P, int accumulate, qba_stream stream) {
+  return lists_call("qba_sample_check", 1, BYTE_ROWS, ctx, n, seed, first, count, lists, ld, H, C, P, accumulate,
+                    stream);
+}
+
+extern "C" int qba_sample_check_deferred(qba_ctx *ctx, int n, uint64_t seed, uint64_t first, uint64_t count,
+                                         uint8_t *lists, uint64_t ld, int64_t *H, int64_t *C, int64_t *P,
+                                         int accumulate, qba_stream stream) {
+  return lists_call("qba_sample_check_deferred", 1, BYTE_ROWS | DEFER, ctx, n, seed, first, count, lists, ld, H, C, P,
+                    accumulate, stream);
+}
+
+extern "C" int qba_check_counts(qba_ctx *ctx, int n, const uint8_t *lists, uint64_t count, uint64_t ld, int64_t *H,
                                 int64_t *C, int64_t *P, int accumulate, qba_stream stream) {
-  int rc = check_common(ctx, n, lists, count, ld, "qba_sample_check");
-  if (rc) return rc;
-  if (!H || !C || !P) return qba_fail(QBA_EINVAL, "qba_sample_check: H, C and P are required");
-  if (count == 0)
-    return accumulate ? qba_flush_pending(ctx, (hipStream_t)stream) : zero_counts(ctx, n, H, C, P, (hipStream_t)stream);
-  if ((rc = need_program(ctx, n, "qba_sample_check"))) return rc;
-  QbaLaunch L{n, 1, (const QbaProgramSet *)ctx->prog_dev[n], seed, first, count, lists, ld,
-              H, C, P, ctx->stats, accumulate, (hipStream_t)stream};
-  return dispatch(ctx, L);
-}
-
-extern "C" int qba_sample_check_deferred(qba_ctx *ctx, int n, uint64_t seed, uint64_t first,
-                                         uint64_t count, uint8_t *lists, uint64_t ld, int64_t *H,
-                                         int64_t *C, int64_t *P, int accumulate, qba_stream stream) {
-  int rc = check_common(ctx, n, lists, count, ld, "qba_sample_check_deferred");
-  if (rc) return rc;
-  if (!H || !C || !P) return qba_fail(QBA_EINVAL, "qba_sample_check_deferred: H, C and P are required");
-  if (count == 0)
-    return accumulate ? qba_flush_pending(ctx, (hipStream_t)stream) : zero_counts(ctx, n, H, C, P, (hipStream_t)stream);
-  if ((rc = need_program(ctx, n, "qba_sample_check_deferred"))) return rc;
-  QbaLaunch L{n, 1, (const QbaProgramSet *)ctx->prog_dev[n], seed, first, count, lists, ld,
-              H, C, P, ctx->stats, accumulate, (hipStream_t)stream, 0, 0, 1};
-  return dispatch(ctx, L);
-}
-
-extern "C" int qba_check_counts(qba_ctx *ctx, int n, const uint8_t *lists, uint64_t count,
-                                uint64_t ld, int64_t *H, int64_t *C, int64_t *P, int accumulate,
-                                qba_stream stream) {
-  int rc = check_common(ctx, n, lists, count, ld, "qba_check_counts");
-  if (rc) return rc;
-  if (!H || !C || !P) return qba_fail(QBA_EINVAL, "qba_check_counts: H, C and P are required");
-  if (count == 0)
-    return accumulate ? qba_flush_pending(ctx, (hipStream_t)stream) : zero_counts(ctx, n, H, C, P, (hipStream_t)stream);
-  QbaLaunch L{n, 2, nullptr, 0, 0, count, const_cast<uint8_t *>(lists), ld,
-              H, C, P, ctx->stats, accumulate, (hipStream_t)stream};
-  return dispatch(ctx, L);
+  return lists_call("qba_check_counts", 2, BYTE_ROWS, ctx, n, 0, 0, count, const_cast<uint8_t *>(lists), ld, H, C, P,
+                    accumulate, stream);
 }
 
 // ---- nibble rows ("packed lists", qba.h) ----------------------------------------
-extern "C" int qba_sample_packed(qba_ctx *ctx, int n, uint64_t seed, uint64_t first, uint64_t count,
-                                 uint8_t *packed, uint64_t ldp, qba_stream stream) {
-  int rc = check_common(ctx, n, packed, count, ldp, "qba_sample_packed", true);
-  if (rc || count == 0) return rc;
-  if ((rc = need_program(ctx, n, "qba_sample_packed"))) return rc;
-  QbaLaunch L{n, 0, (const QbaProgramSet *)ctx->prog_dev[n], seed, first, count, packed, ldp,
-              nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, 0, 1};
-  return dispatch(ctx, L);
+extern "C" int qba_sample_packed(qba_ctx *ctx, int n, uint64_t seed, uint64_t first, uint64_t count, uint8_t *packed,
+                                 uint64_t ldp, qba_stream stream) {
+  return lists_call("qba_sample_packed", 0, NIBBLE_ROWS, ctx, n, seed, first, count, packed, ldp, nullptr, nullptr,
+                    nullptr, 0, stream);
 }
 
-extern "C" int qba_sample_check_packed(qba_ctx *ctx, int n, uint64_t seed, uint64_t first,
-                                       uint64_t count, uint8_t *packed, uint64_t ldp, int64_t *H,
-                                       int64_t *C, int64_t *P, int accumulate, qba_stream stream) {
-  int rc = check_common(ctx, n, packed, count, ldp, "qba_sample_check_packed", true);
-  if (rc) return rc;
-  if (!H || !C || !P) return qba_fail(QBA_EINVAL, "qba_sample_check_packed: H, C and P are required");
-  if (count == 0)
-    return accumulate ? qba_flush_pending(ctx, (hipStream_t)stream) : zero_counts(ctx, n, H, C, P, (hipStream_t)stream);
-  if ((rc = need_program(ctx, n, "qba_sample_check_packed"))) return rc;
-  QbaLaunch L{n, 1, (const QbaProgramSet *)ctx->prog_dev[n], seed, first, count, packed, ldp,
-              H, C, P, ctx->stats, accumulate, (hipStream_t)stream, 0, 1};
-  return dispatch(ctx, L);
+extern "C" int qba_sample_check_packed(qba_ctx *ctx, int n, uint64_t seed, uint64_t first, uint64_t count,
+                                       uint8_t *packed, uint64_t ldp, int64_t *H, int64_t *C, int64_t *P,
+                                       int accumulate, qba_stream stream) {
+  return lists_call("qba_sample_check_packed", 1, NIBBLE_ROWS, ctx, n, seed, first, count, packed, ldp, H, C, P,
+                    accumulate, stream);
 }
 
-extern "C" int qba_sample_check_packed_deferred(qba_ctx *ctx, int n, uint64_t seed, uint64_t first,
-                                                uint64_t count, uint8_t *packed, uint64_t ldp, int64_t *H,
-                                                int64_t *C, int64_t *P, int accumulate, qba_stream stream) {
-  int rc = check_common(ctx, n, packed, count, ldp, "qba_sample_check_packed_deferred", true);
-  if (rc) return rc;
-  if (!H || !C || !P) return qba_fail(QBA_EINVAL, "qba_sample_check_packed_deferred: H, C and P are required");
-  if (count == 0)
-    return accumulate ? qba_flush_pending(ctx, (hipStream_t)stream) : zero_counts(ctx, n, H, C, P, (hipStream_t)stream);
-  if ((rc = need_program(ctx, n, "qba_sample_check_packed_deferred"))) return rc;
-  QbaLaunch L{n, 1, (const QbaProgramSet *)ctx->prog_dev[n], seed, first, count, packed, ldp,
-              H, C, P, ctx->stats, accumulate, (hipStream_t)stream, 0, 1, 1};
-  return dispatch(ctx, L);
+extern "C" int qba_sample_check_packed_deferred(qba_ctx *ctx, int n, uint64_t seed, uint64_t first, uint64_t count,
+                                                uint8_t *packed, uint64_t ldp, int64_t *H, int64_t *C, int64_t *P,
+                                                int accumulate, qba_stream stream) {
+  return lists_call("qba_sample_check_packed_deferred", 1, NIBBLE_ROWS | DEFER, ctx, n, seed, first, count, packed, ldp,
+                    H, C, P, accumulate, stream);
 }
 
-extern "C" int qba_check_counts_packed(qba_ctx *ctx, int n, const uint8_t *packed, uint64_t count,
-                                       uint64_t ldp, int64_t *H, int64_t *C, int64_t *P, int accumulate,
-                                       qba_stream stream) {
-  int rc = check_common(ctx, n, packed, count, ldp, "qba_check_counts_packed", true);
-  if (rc) return rc;
-  if (!H || !C || !P) return qba_fail(QBA_EINVAL, "qba_check_counts_packed: H, C and P are required");
-  if (count == 0)
-    return accumulate ? qba_flush_pending(ctx, (hipStream_t)stream) : zero_counts(ctx, n, H, C, P, (hipStream_t)stream);
-  QbaLaunch L{n, 2, nullptr, 0, 0, count, const_cast<uint8_t *>(packed), ldp,
-              H, C, P, ctx->stats, accumulate, (hipStream_t)stream, 0, 1};
-  return dispatch(ctx, L);
+extern "C" int qba_check_counts_packed(qba_ctx *ctx, int n, const uint8_t *packed, uint64_t count, uint64_t ldp,
+                                       int64_t *H, int64_t *C, int64_t *P, int accumulate, qba_stream stream) {
+  return lists_call("qba_check_counts_packed", 2, NIBBLE_ROWS, ctx, n, 0, 0, count, const_cast<uint8_t *>(packed), ldp,
+                    H, C, P, accumulate, stream);
 }
 
 // Byte rows <-> nibble rows, one packed byte per thread (conversion helpers,

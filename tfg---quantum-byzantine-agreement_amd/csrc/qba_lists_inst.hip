@@ -1,6 +1,7 @@
 // qba_lists_inst.hip -- one n's list kernels and launchers; built once per
 // n = 1..15 with -DQBA_INST_N=n (csrc/Makefile), in parallel.
 #include "qba_lists_kern.h"
+#include "qba_lists_launch.h"
 
 #ifndef QBA_INST_N
 #error "build with -DQBA_INST_N=<n>"

@@ -1,5 +1,6 @@
-// qba_lists_kern.h -- the data-parallel hot path on gfx950 (kernels and their
-// per-n launchers; instantiated by qba_lists_inst.hip):
+// qba_lists_kern.h -- the data-parallel hot path on gfx950: the device code
+// only (its per-n launchers are qba_lists_launch.h; both are instantiated by
+// qba_lists_inst.hip):
 //   * Born sampling of list entries (tfg.py:68-84 + 128-129) from the compiled
 //     factored alias-table program, Philox4x32-10 keyed by the global entry;
 //   * the count-mode check pass (tfg.py:87-98, 182, 189, 291-294, 327):
@@ -686,11 +687,20 @@ __device__ __forceinline__ qba_lds_u32 *qba_lds(uint32_t addr) {
 }
 
 // The queue area starts after the histogram, aligned to one ring (the host
-// sizes the launch's LDS with QBA_QCAP * 4 bytes of slack for it).
+// sizes the launch's LDS with QBA_QCAP * 4 bytes of slack for it:
+// qba_count_lds).
 template <int NP>
 __device__ __forceinline__ uint32_t qba_queue_base(uint32_t *hist) {
   const uint32_t h = (uint32_t)(uintptr_t)(qba_lds_u32 *)hist + ((QCfg<NP>::NBP + 3) & ~3) * 4;
   return (h + QBA_QCAP * 4 - 1) & ~(uint32_t)(QBA_QCAP * 4 - 1);
+}
+// LDS bytes of a counting workgroup of bs threads after its staged tables, as
+// qba_queue_base and the kernels' wq.base lay them out: the histogram, the
+// ring alignment's slack, one ring [ND][QBA_QCAP] per wave.
+template <int NP>
+__host__ __device__ constexpr size_t qba_count_lds(int bs) {
+  static_assert(QCfg<NP>::NBP % 4 == 0, "the histogram is whole 16-B words");
+  return (size_t)QCfg<NP>::NBP * 4 + QBA_QCAP * 4 + (size_t)(bs / 64) * CF<NP>::ND * QBA_QCAP * 4;
 }
 
 // Count the nv (<= 64) oldest queued entries, one per lane.  TRUSTED: the
@@ -779,6 +789,13 @@ struct QbaPB {
   static constexpr int AREA = WORDS + MISC;
   static constexpr int QSLOT = 8;          // queue bytes per entry
 };
+// LDS bytes of a pair-bin workgroup of bs threads after its staged tables, as
+// qba_lists_body (CNT) lays them out: up to 1 KiB to align array A, the bins,
+// the ring alignment's slack (one ring), one ring [QBA_QCAP] of 8-B slots per wave.
+__host__ __device__ constexpr size_t qba_pb_lds(int bs) {
+  static_assert(QbaPB::QSLOT == 8, "qba_lists_body places the rings QBA_QCAP * 8 bytes apart");
+  return 1024 + (size_t)QbaPB::AREA * 4 + (size_t)(bs / 64 + 1) * QBA_QCAP * QbaPB::QSLOT;
+}
 // the kernels that count with pair bins: the fused closed-form n = 11 kernel
 // and the n = 11 check of nibble rows (every value < 16 = w, so no range test)
 template <int NP, int MODE, int SAMP, int PK>
@@ -1230,7 +1247,8 @@ __device__ __forceinline__ void qba_step_l(uint32_t c0, uint32_t count, uint64_t
     qba_step<NP, MODE, SAMP, QPT, TAIL, WQ, CNT, PW>(c0, count, first, k0, k1, ps, pat, apat, thr, pl, lists, ld, hist, wq, act);
 }
 
-// Stage the program's tables in LDS; returns the histogram base after them.
+// Stage the program's tables in LDS; returns the histogram base after them
+// (their bytes on the host: table_lds, qba_lists_launch.h).
 template <int NP, int MODE, int SAMP, int BS>
 __device__ __forceinline__ uint32_t *qba_stage(const QbaProgramSet *__restrict__ ps, uint64_t *lds,
                                                const uint64_t *&pat, const uint64_t *&apat,
@@ -1399,6 +1417,8 @@ __device__ __forceinline__ void qba_lists_body(const QbaProgramSet *__restrict__
   const uint64_t *pat, *apat, *thr;
   const uint32_t *pl;
   uint32_t *hist = qba_stage<NP, MODE, SAMP, BS>(ps, lds, pat, apat, thr, pl);
+  // the launcher sizes what follows the tables: qba_count_lds, CNT: qba_pb_lds
+  static_assert(!CNT || C::NBP <= QbaPB::AREA, "a wrapped workgroup recounts into classic bins in the pair bins' place");
   if constexpr (CNT) {  // pair bins: array A 1-KiB aligned (qba_count_pb ORs 64 u into its address)
     const uint32_t h = (uint32_t)(uintptr_t)(qba_lds_u32 *)hist;
     hist += (((h + 1023u) & ~1023u) - h) / 4;
@@ -1558,8 +1578,13 @@ __host__ __device__ constexpr int qba_def_wgs() {  // reduce workgroups of one d
   return QCfg<NP>::W * qba_def_parts<NP>();
 }
 
+// LDS bytes of qba_reduce_u's scratch for a workgroup of bs threads
+template <int NP>
+__host__ __device__ constexpr size_t qba_reduce_lds(int bs) {
+  return (size_t)(bs + qba_def_cols<NP>(0)) * sizeof(uint32_t);
+}
 // The reduce of part `part` of bin row u by one workgroup of bs threads; sh:
-// LDS scratch of (bs + qba_def_cols(0)) words.
+// LDS scratch of (bs + qba_def_cols(0)) words (qba_reduce_lds).
 template <int NP>
 __device__ __forceinline__ void qba_reduce_u(const QbaDefer &d, int u, int part, int tid, int bs, uint32_t *sh) {
   using C = QCfg<NP>;
@@ -1819,322 +1844,3 @@ __global__ void __launch_bounds__(256)
     atomicAdd(reinterpret_cast<u64 *>(dst), v);
   }
 }
-
-// ---------------------------------------------------------------------------
-// per-n launchers
-// ---------------------------------------------------------------------------
-
-// Persistent grid: every resident workgroup slot of the chip (LDS- and
-// register-limited occupancy), fewer when the launch has less work.
-static int grid_for(qba_ctx *ctx, const void *kern, size_t lds, uint64_t count, int qpt = QBA_GRID_QPT,
-                    int *cap_out = nullptr, int bs = QBA_LBLOCK) {
-  // the occupancy query costs tens of microseconds: cached per (kernel, LDS)
-  struct Occ {
-    const void *k;
-    size_t lds;
-    int per_cu;
-  };
-  static thread_local Occ cache[16] = {};
-  static thread_local int next = 0;
-  int per_cu = 0;
-  for (const Occ &o : cache)
-    if (o.k == kern && o.lds == lds) per_cu = o.per_cu;
-  if (per_cu == 0) {
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, bs, lds) != hipSuccess ||
-        per_cu < 1)
-      per_cu = 1;
-    cache[next] = Occ{kern, lds, per_cu};
-    next = (next + 1) % 16;
-  }
-  const uint64_t nquad = (count + 3) >> 2;
-  // >= 2 quads (one wide thread-step) per thread: a small launch (configs[1],
-  // 1e6 entries) spreads over 163 workgroups instead of 82
-  uint64_t g = (nquad + (uint64_t)qpt * bs - 1) / ((uint64_t)qpt * bs);
-  const uint64_t cap = (uint64_t)ctx->num_cus * (uint64_t)per_cu;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  if (cap_out) *cap_out = (int)cap;
-  return (int)g;
-}
-
-// qba_flush_deferred / qba_flush_pending: the pending call's reduction alone.
-template <int NP>
-static int qba_flush_def(qba_ctx *ctx) {
-  const auto &p = ctx->pend;
-  const QbaDefer d{p.slab, p.rows, 0, p.acc, p.sacc, p.H, p.C, p.P, p.stats};
-  const size_t lds = (size_t)(QBA_LBLOCK + qba_def_cols<NP>(0)) * sizeof(uint32_t);
-  hipLaunchKernelGGL(qba_k_reduce_def<NP>, dim3(qba_def_wgs<NP>()), dim3(QBA_LBLOCK), lds, p.stream, d);
-  QBA_HIP(hipGetLastError());
-  return QBA_OK;
-}
-
-// Sampler of the compiled pair: closed form when proven (n <= 11), else the
-// canonical-table fast path, else the general alias-table path.
-template <int NP>
-static int sampler_of(const QbaProgramSet *hs) {
-  if (NP <= QBA_CLOSED_MAX_N && hs->closed) return QBA_S_CLOSED;
-  return hs->canonical ? QBA_S_FAST : QBA_S_GENERAL;
-}
-
-// LDS bytes of the staged tables for a sampling launch
-template <int NP>
-static size_t table_lds(const QbaProgramSet *hs, int samp) {
-  if (samp == QBA_S_CLOSED) return (size_t)((CF<NP>::WORDS + 3) & ~3) * sizeof(uint32_t);
-  return (size_t)(((hs->any_nonuniform ? 3 : 1) * hs->table_total + 1) & ~1) * sizeof(uint64_t);
-}
-
-template <int NP>
-static int check_closed(const QbaProgramSet *hs) {
-  if (hs->closed && (hs->ra != CF<NP>::RA || hs->rb != CF<NP>::RB || hs->rc != CF<NP>::RC ||
-                     hs->perm_words != CF<NP>::WORDS || hs->t32 != CF<NP>::T32 ||
-                     hs->perm_off != (int32_t)QBA_PERM_OFF))
-    return qba_fail(QBA_EINVAL, "closed-form program does not match the kernel's stage layout");
-  return QBA_OK;
-}
-
-template <int NP>
-int qba_launch_lists(qba_ctx *ctx, const QbaLaunch &L) {
-  using C = QCfg<NP>;
-  const QbaProgramSet *hs = reinterpret_cast<const QbaProgramSet *>(ctx->prog_host[NP]);
-  int samp = QBA_S_GENERAL;
-  size_t lds = 0;
-  if (L.mode != 2) {
-    samp = sampler_of<NP>(hs);
-    if (int rc = check_closed<NP>(hs)) return rc;
-    lds += table_lds<NP>(hs, samp);
-  }
-  // the fused closed-form kernel and the check of nibble rows count with
-  // pair bins (QbaPB, n = 11) when the launch is large enough to repay their
-  // flush (a fixed ~2 us per launch: 1e6 entries 17.7 vs 15.0 us, 1.25e8
-  // entries 298 vs 313 us, profiles/r4/small_launch); the tests' list_grid
-  // knob (qba_test_set_knobs) forces them
-  const bool pb = ((L.mode == 1 && QbaUsePB<NP, 1, QBA_S_CLOSED, 0>::value && samp == QBA_S_CLOSED) ||
-                   (L.mode == 2 && QbaUsePB<NP, 2, QBA_S_GENERAL, 1>::value && L.packed)) &&
-                  (L.count >= ctx->pb_min || ctx->list_grid > 0);
-  if (pb) {
-    lds += 1024 + (size_t)QbaPB::AREA * sizeof(uint32_t) + (size_t)(QBA_LBLOCK / 64 + 1) * QBA_QCAP * QbaPB::QSLOT;
-  } else if (L.mode != 0) {
-    lds += (size_t)((C::NBP + 3) & ~3) * sizeof(uint32_t);
-    lds += (size_t)(QBA_LBLOCK / 64) * CF<NP>::ND * QBA_QCAP * sizeof(uint32_t) + QBA_QCAP * 4;
-  }
-  lds = (lds + 15) & ~(size_t)15;
-  if (lds == 0) lds = 16;
-  // 4*QPT-byte row vectors (QPT quads per thread-step) when the rows allow it
-  constexpr uintptr_t VA = 4 * QBA_WIDE_QPT - 1;  // row vectors need their natural alignment
-  // (the one-quad step on twice the workgroups for small launches shortens
-  // the list kernel -- 8.8 vs 10.1 us at 1e6 entries -- but its workgroups
-  // then share CUs with the deferred reduction's: 11.7 vs 10.3 us per
-  // configs[1] step, profiles/r3/r3m, r3n; rejected, tools/exp/rejected)
-  // nibble rows: the wide step stores one 4-B word per row (QPT = 2)
-  const uintptr_t va = L.packed ? 3 : VA;
-  const bool wide = !(reinterpret_cast<uintptr_t>(L.lists) & va) && !(L.ld & va);
-#define QBA_K(M, S)                                                                          \
-  (L.packed ? (wide ? (const void *)qba_k_lists<NP, M, S, 2, 1> : (const void *)qba_k_lists<NP, M, S, 1, 1>) \
-            : (wide ? (const void *)qba_k_lists<NP, M, S, QBA_WIDE_QPT, 0> : (const void *)qba_k_lists<NP, M, S, 1, 0>))
-  const void *kern = nullptr;
-  if (L.mode == 2) {
-    kern = QBA_K(2, QBA_S_GENERAL);
-    if constexpr (QbaUsePB<NP, 2, QBA_S_GENERAL, 1>::value)
-      if (pb)
-        kern = wide ? (const void *)qba_k_lists<NP, 2, QBA_S_GENERAL, 2, 1, 1>
-                    : (const void *)qba_k_lists<NP, 2, QBA_S_GENERAL, 1, 1, 1>;
-  } else if (samp == QBA_S_CLOSED) {
-    if constexpr (NP <= QBA_CLOSED_MAX_N) {
-      kern = L.mode == 0 ? QBA_K(0, QBA_S_CLOSED) : QBA_K(1, QBA_S_CLOSED);
-      if constexpr (QbaUsePB<NP, 1, QBA_S_CLOSED, 0>::value)
-        if (pb)
-          kern = L.packed ? (wide ? (const void *)qba_k_lists<NP, 1, QBA_S_CLOSED, 2, 1, 1>
-                                  : (const void *)qba_k_lists<NP, 1, QBA_S_CLOSED, 1, 1, 1>)
-                          : (wide ? (const void *)qba_k_lists<NP, 1, QBA_S_CLOSED, QBA_WIDE_QPT, 0, 1>
-                                  : (const void *)qba_k_lists<NP, 1, QBA_S_CLOSED, 1, 0, 1>);
-    } else
-      return qba_fail(QBA_EUNSUPPORTED, "closed form beyond n = 11");
-  } else if (samp == QBA_S_FAST) {
-    kern = L.mode == 0 ? QBA_K(0, QBA_S_FAST) : QBA_K(1, QBA_S_FAST);
-  } else {
-    kern = L.mode == 0 ? QBA_K(0, QBA_S_GENERAL) : QBA_K(1, QBA_S_GENERAL);
-  }
-#undef QBA_K
-  if (lds > 65536) QBA_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  int cap = 0;
-  int grid = grid_for(ctx, kern, lds, L.count, wide ? (L.packed ? 2 : QBA_GRID_QPT) : 1, &cap);
-  if (ctx->list_grid > 0 && grid > ctx->list_grid) grid = ctx->list_grid;  // tests (qba_test_set_knobs)
-  // pair bins: at most QBA_PB_BUDGET entries per workgroup and launch (QbaPB;
-  // a grid capped by the tests' list_grid knob -- tests that force wraps --
-  // at most 2^23, so group 0's 24-bit total, which counts every entry of the
-  // workgroup once, stays exact)
-  const uint64_t pb_part = ctx->list_grid ? (uint64_t)grid << QBA_PB_FORCED_LOG2 : (uint64_t)cap * QBA_PB_BUDGET;
-  if (pb && L.count > pb_part) {
-    // later parts accumulate; part boundaries are multiples of 2^18 entries,
-    // so the row alignment and the pair parity of `first` are those of the
-    // call; only the last part of a deferred call defers its reduction
-    const uint64_t part = pb_part;
-    QbaLaunch S = L;
-    int rc = QBA_OK;
-    for (uint64_t done = 0; !rc && done < L.count; done += S.count) {
-      S.count = L.count - done < part ? L.count - done : part;
-      S.defer = done + S.count >= L.count ? L.defer : 0;
-      S.first = L.first + done;
-      S.lists = L.lists + (L.packed ? done >> 1 : done);
-      S.accumulate = done ? 1 : L.accumulate;
-      S.stats_accumulate = done ? 1 : L.stats_accumulate;
-      rc = qba_launch_lists<NP>(ctx, S);
-    }
-    return rc;
-  }
-  const uint32_t k0 = (uint32_t)L.seed, k1 = (uint32_t)(L.seed >> 32);
-  const QbaProgramSet *ps = L.ps;
-  uint64_t first = L.first;
-  uint32_t count = (uint32_t)L.count;
-  uint8_t *lists = L.lists;
-  uint64_t ld = L.ld;
-  // Deferred reduction: the list kernel also reduces the pending deferred
-  // call (W workgroups after its own) when both fit the chip's resident
-  // slots together; otherwise the pending one is flushed and this call is
-  // reduced at once (its results are then simply complete earlier).
-  const void *kd = nullptr;
-  // a large pair-bin launch defers into its own tail (qba_k_lists_pbdef)
-  const bool pbd = pb && L.defer && L.mode == 1;
-  if constexpr (QbaUsePB<NP, 1, QBA_S_CLOSED, 0>::value)
-    if (pbd)
-      kd = L.packed ? (wide ? (const void *)qba_k_lists_pbdef<NP, 2, 1> : (const void *)qba_k_lists_pbdef<NP, 1, 1>)
-                    : (wide ? (const void *)qba_k_lists_pbdef<NP, QBA_WIDE_QPT, 0>
-                            : (const void *)qba_k_lists_pbdef<NP, 1, 0>);
-  if (!pbd && L.defer && L.mode == 1) {
-#define QBA_KD(S)                                                                                  \
-  (L.packed ? (wide ? (const void *)qba_k_lists_def<NP, S, 2, 1> : (const void *)qba_k_lists_def<NP, S, 1, 1>) \
-            : (wide ? (const void *)qba_k_lists_def<NP, S, QBA_WIDE_QPT, 0> : (const void *)qba_k_lists_def<NP, S, 1, 0>))
-    if (samp == QBA_S_CLOSED) {
-      if constexpr (NP <= QBA_CLOSED_MAX_N) kd = QBA_KD(QBA_S_CLOSED);
-    } else {
-      kd = samp == QBA_S_FAST ? QBA_KD(QBA_S_FAST) : QBA_KD(QBA_S_GENERAL);
-    }
-#undef QBA_KD
-  }
-  // the deferred kernel runs QBA_DBLOCK-thread workgroups (small launches:
-  // more, shorter workgroups; 9.6 vs 10.5 us per configs[1] pass)
-  size_t dlds = 0;
-  int dgrid = 0, dcap = 0;
-  if (pbd) {  // the list kernel's own launch shape; its LDS covers a reduce workgroup's scratch
-    dlds = lds;
-    if (dlds < (size_t)(QBA_LBLOCK + qba_def_cols<NP>(0)) * sizeof(uint32_t))
-      dlds = (size_t)(QBA_LBLOCK + qba_def_cols<NP>(0)) * sizeof(uint32_t);
-    if (dlds > 65536) QBA_HIP(hipFuncSetAttribute(kd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds));
-    dgrid = grid;
-  } else if (kd) {
-    dlds = table_lds<NP>(hs, samp) +
-           (size_t)((C::NBP + 3) & ~3) * sizeof(uint32_t);
-    dlds += (size_t)(QBA_DBLOCK / 64) * CF<NP>::ND * QBA_QCAP * sizeof(uint32_t) + QBA_QCAP * 4;
-    const size_t rlds = (size_t)(QBA_DBLOCK + qba_def_cols<NP>(0)) * sizeof(uint32_t);
-    if (dlds < rlds) dlds = rlds;
-    dlds = (dlds + 15) & ~(size_t)15;
-    if (dlds > 65536) QBA_HIP(hipFuncSetAttribute(kd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds));
-    dgrid = grid_for(ctx, kd, dlds, L.count, wide ? (L.packed ? 2 : QBA_GRID_QPT) : 1, &dcap, QBA_DBLOCK);
-    // a launch that would leave CUs idle spreads its units over one workgroup
-    // per CU (wave-major units, qba_lists_body): the LDS work of its counting
-    // is what bounds it (configs[1]: 163 -> 256 workgroups)
-    if (dgrid < ctx->num_cus && ctx->num_cus + qba_def_wgs<NP>() <= dcap) dgrid = ctx->num_cus;
-  }
-  if (kd && (pbd || dgrid + qba_def_wgs<NP>() <= dcap)) {
-    const int grid = dgrid;
-    auto &pd = ctx->pend;
-    int rc = QBA_OK;
-    // a pending call of another n or on another stream is flushed on its own
-    // (qba_flush_pending refuses one recorded in another capture state)
-    if (pd.flush && (pd.flush != &qba_flush_def<NP> || pd.stream != L.stream))
-      if ((rc = qba_flush_pending(ctx, L.stream))) return rc;
-    unsigned long long cid = 0;
-    const int cap = qba_capture_of(L.stream, &cid);
-    if (pd.flush && (cap != ctx->pend_captured || (cap && cid != ctx->pend_capture_id)))
-      return qba_fail(QBA_ESTATE, "a deferred reduction is pending across a graph-capture boundary: call "
-                                  "qba_flush_deferred before beginning and before ending a capture");
-    if (!pd.flush && (rc = qba_slab_order(ctx, L.stream))) return rc;
-    const size_t half_need = ((size_t)grid * C::NBP * sizeof(uint32_t) + 255) & ~(size_t)255;
-    if (ctx->slab_bytes < 2 * half_need) {
-      if ((rc = qba_flush_pending(ctx, L.stream))) return rc;
-      if ((rc = qba_ensure_slab(ctx, 2 * half_need))) return rc;  // synchronises before a reallocation
-    }
-    const size_t half = (ctx->slab_bytes / 2) & ~(size_t)255;
-    const int red = pd.flush ? qba_def_wgs<NP>() : 0;
-    const int buf = pd.flush ? pd.buf ^ 1 : 0;
-    uint32_t *slab = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(ctx->slab) + (size_t)buf * half);
-    QbaDefer d{pd.slab, pd.rows, red, pd.acc, pd.sacc, pd.H, pd.C, pd.P, pd.stats};
-    QbaZero zero{L.H, L.C, L.P, L.stats, 0u};  // the reduction writes every output word itself
-    void *args[] = {&ps, (void *)&k0, (void *)&k1, &first, &count, &lists, &ld, &slab, &zero, &d};
-    QBA_HIP(hipLaunchKernel(kd, dim3(grid + red), dim3(pbd ? QBA_LBLOCK : QBA_DBLOCK), args, dlds, L.stream));
-    QBA_HIP(hipGetLastError());
-    pd.flush = &qba_flush_def<NP>;
-    pd.slab = slab;
-    pd.rows = grid;
-    pd.acc = L.accumulate;
-    pd.sacc = L.stats_accumulate;
-    pd.buf = buf;
-    pd.H = L.H;
-    pd.C = L.C;
-    pd.P = L.P;
-    pd.stats = L.stats;
-    pd.stream = L.stream;
-    ctx->pend_captured = cap;
-    ctx->pend_capture_id = cid;
-    return qba_slab_done(ctx, L.stream);
-  }
-  if (L.mode != 0) {
-    if (int rc = qba_flush_pending(ctx, L.stream)) return rc;
-    if (int rc = qba_slab_order(ctx, L.stream)) return rc;
-  }
-  uint32_t *slab = nullptr;
-  if (L.mode != 0) {
-    int rc = qba_ensure_slab(ctx, (size_t)grid * C::NBP * sizeof(uint32_t));
-    if (rc) return rc;
-    slab = reinterpret_cast<uint32_t *>(ctx->slab);
-  }
-  QbaZero zero{L.H, L.C, L.P, L.stats,
-               (L.mode != 0 && !L.accumulate ? 1u : 0u) | (L.mode != 0 && !L.stats_accumulate ? 2u : 0u)};
-  void *args[] = {&ps, (void *)&k0, (void *)&k1, &first, &count, &lists, &ld, &slab, &zero};
-  QBA_HIP(hipLaunchKernel(kern, dim3(grid), dim3(QBA_LBLOCK), args, lds, L.stream));
-  QBA_HIP(hipGetLastError());
-  if (L.mode == 0) return QBA_OK;
-  // (qba_k_reduce_def as the synchronous reduce: 6.4 vs 5.5 us at 512 slab
-  // rows, profiles/r3/r3p -- the atomic column reduce stays)
-  const dim3 rgrid((C::NBP / 4 + 255) / 256, (grid + QBA_RED_ROWS - 1) / QBA_RED_ROWS);
-  hipLaunchKernelGGL(qba_k_reduce<NP>, rgrid, dim3(256), 0, L.stream, slab, grid, L.H, L.C, L.P, L.stats);
-  QBA_HIP(hipGetLastError());
-  return qba_slab_done(ctx, L.stream);
-}
-
-template <int NP>
-int qba_launch_batched(qba_ctx *ctx, const QbaBatch &B) {
-  using C = QCfg<NP>;
-  const QbaProgramSet *hs = reinterpret_cast<const QbaProgramSet *>(ctx->prog_host[NP]);
-  const int samp = sampler_of<NP>(hs);
-  if (int rc = check_closed<NP>(hs)) return rc;
-  size_t lds = table_lds<NP>(hs, samp) + (size_t)((C::NBP + 3) & ~3) * sizeof(uint32_t);
-  lds += (size_t)(QBA_BLOCK / 64) * CF<NP>::ND * QBA_QCAP * sizeof(uint32_t) + QBA_QCAP * 4;
-  lds = (lds + 15) & ~(size_t)15;
-  const int64_t cap = (int64_t)ctx->num_cus * 16;
-  // 8-B row vectors (two quads per thread-step; 4 B for nibble rows) when
-  // every row start allows it
-  const uintptr_t VA = B.packed ? 3 : 4 * QBA_WIDE_QPT - 1;
-  const bool wide = !(reinterpret_cast<uintptr_t>(B.lists) & VA) && !(B.ld & VA) && !(B.inst_stride & VA);
-  const int grid = (int)(B.n_inst < cap ? B.n_inst : cap);
-  auto go = [&](auto kern) -> int {
-    if (lds > 65536)
-      QBA_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(QBA_BLOCK), lds, B.stream, B.ps, B.seed_base,
-                       B.n_inst, B.count, B.lists, B.ld, B.inst_stride, B.H, B.C, B.P);
-    QBA_HIP(hipGetLastError());
-    return QBA_OK;
-  };
-#define QBA_B(S)                                                                                   \
-  (B.packed ? (wide ? go(qba_k_batched<NP, S, 2, 1>) : go(qba_k_batched<NP, S, 1, 1>))                    \
-            : (wide ? go(qba_k_batched<NP, S, QBA_WIDE_QPT, 0>) : go(qba_k_batched<NP, S, 1, 0>)))
-  if (samp == QBA_S_CLOSED) {
-    if constexpr (NP <= QBA_CLOSED_MAX_N) return QBA_B(QBA_S_CLOSED);
-    return qba_fail(QBA_EUNSUPPORTED, "closed form beyond n = 11");
-  }
-  if (samp == QBA_S_FAST) return QBA_B(QBA_S_FAST);
-  return QBA_B(QBA_S_GENERAL);
-#undef QBA_B
-}
-
