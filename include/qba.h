@@ -257,6 +257,41 @@ QBA_API int qba_protocol_batched(qba_ctx *ctx, int n_parties, int n_dishonest, u
                                  int64_t n_instances, const int64_t *H_dev, const int64_t *C_dev,
                                  const int64_t *P_dev, int32_t *out_dev, qba_stream stream);
 
+/* The fused Monte-Carlo path: from lists to decision rows in one kernel, with
+ * no list buffer and no count tables in between.  Everything the rounds
+ * consult of an instance's tables is a bitwise reduction over its
+ * Q-correlated entries (L0 != L1, u = L1), so a wavefront ORs / ANDs the
+ * entries into masks in LDS and runs the rounds on those.  Both calls write
+ * exactly the rows of qba_protocol_batched on the tables of the same lists
+ * (row layout and status bits as above), instance i under key seed_base + i
+ * (mod 2^64) for the sampler over entries [0, count) and for the protocol
+ * streams.  count == 0 is valid: every P_u is empty.
+ * n_parties, n_dishonest (as qba_protocol_batched) and count < 2^31 are
+ * checked before ctx, else QBA_EINVAL.  Asynchronous on `stream`, allocate
+ * nothing.
+ *
+ * qba_montecarlo_sampled samples the entries itself, bit for bit those of
+ * qba_sample_check_batched; it needs both resource programs of n_parties
+ * compiled (QBA_ESTATE otherwise). */
+QBA_API int qba_montecarlo_sampled(qba_ctx *ctx, int n_parties, int n_dishonest, uint64_t seed_base,
+                                   int64_t n_instances, uint64_t count, int32_t *out_dev, qba_stream stream);
+
+/* qba_montecarlo_lists reads injected byte rows in the layout of
+ * qba_sample_check_batched (instance i at lists_dev + i*inst_stride, rows ld
+ * apart; ld >= count, inst_stride >= (n+1)*ld, no alignment required) and
+ * needs no program.  status bit 2 (value 4): a list value >= w at a
+ * Q-correlated position -- the lists count mode cannot evaluate
+ * (qba_last_stats) -- and the instance's other fields are 0. */
+QBA_API int qba_montecarlo_lists(qba_ctx *ctx, int n_parties, int n_dishonest, uint64_t seed_base,
+                                 int64_t n_instances, uint64_t count, const uint8_t *lists_dev, uint64_t ld,
+                                 uint64_t inst_stride, int32_t *out_dev, qba_stream stream);
+
+/* The launch shape of qba_montecarlo_sampled for the circuits of
+ * qba_resource_compile's standard programs: wavefronts per workgroup, dynamic
+ * LDS bytes of a workgroup, and the workgroups a CU's 160 KiB hold (DESIGN.md
+ * section 13).  Host only; ctx is not needed. */
+QBA_API int qba_montecarlo_shape(int n_parties, int *waves, int64_t *lds_bytes, int *wgs_per_cu);
+
 /* ---- (A5-A8) checks, exact-order mode (bit-exact protocol parity) --------------- */
 /* isQCorrList = {k : Li[k] != Lc[k]} (tfg.py:327) as ascending indices.
  * *count_host receives the number found; at most `cap` are written. Synchronous. */

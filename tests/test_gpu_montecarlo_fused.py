@@ -1,0 +1,253 @@
+"""The fused Monte-Carlo path on the GPU: qba_montecarlo_sampled and
+qba_montecarlo_lists write exactly the rows of the tables path
+(protocol_batched on the tables of sample_check_batched / count_tables) and of
+the host reference (montecarlo.run_host), in every field of every instance."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, ROOT, sub
+from montecarlo_cases import (CASES, HOSTILE, HOSTILE_IDS, INJECT_BASE, INJECT_KEYS, SWEEP, SWEEP_IDS,
+                              hostile_lists)
+from oracle_engine import OracleEngine
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN_CASES = json.loads((GOLDEN / "protocol.json").read_text())
+GOLDEN_LISTS = np.load(GOLDEN / "protocol_lists.npz")
+NS = [1, 2, 3, 7, 11, 12, 15]
+SIZES = [0, 1, 3, 63, 64, 65, 130, 1000, 4097]
+GRID_INST, GRID_BASE = 67, 0xA11CE
+
+
+def _nd(n, i):
+    """n_dishonest of grid point i: {0, 1, n // 3, n - 1} in turn."""
+    return min(max((0, 1, n // 3, n - 1)[i % 4], 0), n)
+
+
+GRID = [(n, s, _nd(n, i + j)) for i, n in enumerate(NS) for j, s in enumerate(SIZES)]
+
+
+def _eq(got, want, what=""):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape and got.dtype == np.int32
+    if not np.array_equal(got, want):
+        i, j = np.argwhere(got != want)[0]
+        raise AssertionError(f"{what} instance {i}, word {j}: {got[i, j]} != {want[i, j]}\n"
+                             f"got  {got[i].tolist()}\nwant {want[i].tolist()}")
+
+
+def tables_rows(engine, n, nd, base, inst, sizeL, keep_lists=False):
+    """The parent path's rows.  For sizeL = 0 the batched sampler writes
+    nothing, and the rows are defined on all-zero tables."""
+    lists, counts = engine.sample_check_batched(n, base, inst, sizeL)
+    if sizeL == 0:
+        for t in (counts.H, counts.C, counts.P):
+            t.zero_()
+    rows = engine.protocol_batched(n, nd, base, counts).cpu().numpy()
+    rows.setflags(write=False)
+    return (rows, lists) if keep_lists else rows
+
+
+@pytest.fixture(scope="module")
+def grid(engine):
+    memo = {}
+
+    def get(point):
+        if point not in memo:
+            n, sizeL, nd = point
+            memo[point] = tables_rows(engine, n, nd, GRID_BASE, GRID_INST, sizeL)
+        return memo[point]
+    return get
+
+
+@pytest.mark.parametrize("point", GRID, ids=[f"n{n}-L{s}-d{d}" for n, s, d in GRID])
+def test_sampled_form_equals_the_tables_path(engine, grid, point):
+    n, sizeL, nd = point
+    got = engine.montecarlo_sampled(n, nd, GRID_BASE, GRID_INST, sizeL).cpu().numpy()
+    _eq(got, grid(point), f"n={n} sizeL={sizeL} nd={nd}")
+    assert not got[:, 3].any()
+
+
+def test_grid_holds_successes_failures_and_empty_sets(grid):
+    rows = {p: grid(p) for p in GRID}
+    ok = sum(int(r[:, 0].sum()) for r in rows.values())
+    total = sum(len(r) for r in rows.values())
+    assert 0 < ok < total
+    assert {d for _, _, d in GRID} >= {0, 1, 2, 14} and {n <= 11 for n, _, _ in GRID} == {True, False}
+
+
+HOST_CASES = [(c, CASES[c]) for c in CASES if c[0] <= 11] + [((7, 2, 5), (3000, 32))]
+
+
+@pytest.mark.parametrize("case,keys", HOST_CASES, ids=[f"n{c[0]}-d{c[1]}-L{c[2]}" for c, _ in HOST_CASES])
+def test_sampled_form_equals_host_reference(engine, case, keys):
+    mc = sub("montecarlo")
+    n, nd, sizeL = case
+    base, inst = keys
+    want = mc.run_host(n, sizeL, nd, inst, base, OracleEngine())
+    _eq(engine.montecarlo_sampled(n, nd, base, inst, sizeL).cpu().numpy(), want)
+
+
+def test_more_instances_than_resident_wave_slots(engine):
+    n, nd, sizeL, inst, base = 3, 1, 33, 20011, 77
+    got = engine.montecarlo_sampled(n, nd, base, inst, sizeL).cpu().numpy()
+    _eq(got, tables_rows(engine, n, nd, base, inst, sizeL))
+    assert 0 < got[:, 0].sum()
+
+
+def test_key_wraps_mod_2_64(engine):
+    n, nd, sizeL, inst, base = 7, 2, 100, 8, (1 << 64) - 3
+    got = engine.montecarlo_sampled(n, nd, base, inst, sizeL).cpu().numpy()
+    _eq(got, tables_rows(engine, n, nd, base, inst, sizeL))
+    # instances 3.. are those of keys 0..: the wrap is mod 2^64
+    _eq(got[3:], engine.montecarlo_sampled(n, nd, 0, inst - 3, sizeL).cpu().numpy())
+
+
+def _count_rows(engine, n, nd, base, li):
+    """protocol_batched on count_tables of li [keys, n+1, sizeL]."""
+    import torch
+    Counts = sub("engine").Counts
+    keys, g, sizeL = li.shape
+    _, w = engine.sizes(n)
+    h, c = w * g * w, w * g * g
+    distinct = 1 if li.strides[0] == 0 else keys
+    flat = torch.stack([engine.count_tables(n, sizeL, lists=np.array(li[i]), device_out=True)
+                        for i in range(distinct)]).expand(keys, -1)
+    counts = Counts(flat[:, :h].reshape(keys, w, g, w).contiguous(),
+                    flat[:, h:h + c].reshape(keys, w, g, g).contiguous(), flat[:, h + c:].contiguous())
+    return engine.protocol_batched(n, nd, base, counts).cpu().numpy()
+
+
+@pytest.mark.parametrize("case", HOSTILE + SWEEP, ids=HOSTILE_IDS + SWEEP_IDS)
+def test_lists_form_equals_host_and_tables_on_hostile_lists(engine, case):
+    mc = sub("montecarlo")
+    n, nd, sizeL, keys, base = case["n"], case["nDishonest"], case["sizeL"], case["keys"], case["base"]
+    li = hostile_lists(case)
+    got = engine.montecarlo_lists(n, nd, base, np.ascontiguousarray(li), sizeL).cpu().numpy()
+    _eq(got, mc.run_host(n, sizeL, nd, keys, base, OracleEngine(), lists=li), "host:")
+    _eq(got, _count_rows(engine, n, nd, base, li), "tables:")
+    assert not got[:, 3].any()
+
+
+@pytest.mark.parametrize("case", GOLDEN_CASES, ids=[c["name"] for c in GOLDEN_CASES])
+def test_lists_form_equals_host_and_tables_on_golden_lists(engine, case):
+    mc = sub("montecarlo")
+    n, nd, sizeL = case["n"], case["nDishonest"], case["sizeL"]
+    li = np.broadcast_to(GOLDEN_LISTS[case["name"]], (INJECT_KEYS, n + 1, sizeL))
+    got = engine.montecarlo_lists(n, nd, INJECT_BASE, np.ascontiguousarray(li), sizeL).cpu().numpy()
+    _eq(got, mc.run_host(n, sizeL, nd, INJECT_KEYS, INJECT_BASE, OracleEngine(), lists=li), "host:")
+    _eq(got, _count_rows(engine, n, nd, INJECT_BASE, li), "tables:")
+
+
+@pytest.mark.parametrize("n,nd,sizeL", [(3, 1, 60), (11, 3, 400), (15, 2, 400)])
+def test_lists_form_on_the_devices_own_lists_equals_the_sampled_form(engine, n, nd, sizeL):
+    base, inst = 4242, 32
+    rows, lists = tables_rows(engine, n, nd, base, inst, sizeL, keep_lists=True)
+    got = engine.montecarlo_lists(n, nd, base, lists, sizeL).cpu().numpy()   # rows 4 KiB apart, as sampled
+    _eq(got, engine.montecarlo_sampled(n, nd, base, inst, sizeL).cpu().numpy())
+    _eq(got, rows)
+
+
+def test_range_status(engine):
+    mc, QbaError = sub("montecarlo"), sub("_lib").QbaError
+    case = next(c for c in HOSTILE if c["n"] == 3)
+    n, nd, sizeL, base = 3, case["nDishonest"], case["sizeL"], case["base"]
+    w = 4
+    li = np.array(np.broadcast_to(hostile_lists(case)[0], (5, n + 1, sizeL)))
+    li[:, 0, 0] = li[:, 1, 0]                       # entry 0 is not Q-correlated in every instance
+    q = int(np.nonzero(li[2, 0] != li[2, 1])[0][0])  # a Q-correlated entry of instance 2
+    clean = engine.montecarlo_lists(n, nd, base, li, sizeL).cpu().numpy()
+    assert not clean[:, 3].any()
+    mc.summarize(n, clean)
+    bad = li.copy()
+    bad[2, 2, q] = w
+    rows = engine.montecarlo_lists(n, nd, base, bad, sizeL).cpu().numpy()
+    assert rows[2].tolist() == [0, 0, 0, mc.ST_RANGE] + [0] * (5 * (n + 1))
+    _eq(np.delete(rows, 2, 0), np.delete(clean, 2, 0))
+    with pytest.raises(QbaError):
+        mc.summarize(n, rows)
+    for g in (2, 3):                                 # the same value where L0 == L1 changes nothing
+        off = li.copy()
+        off[2, g, 0] = w
+        _eq(engine.montecarlo_lists(n, nd, base, off, sizeL).cpu().numpy(), clean)
+    top = li.copy()                                  # 255 in L1 itself: never used as an index
+    top[2, 1, q] = 255
+    assert engine.montecarlo_lists(n, nd, base, top, sizeL).cpu().numpy()[2, 3] == mc.ST_RANGE
+
+
+def test_out_is_written_in_every_word_and_checked(engine):
+    import torch
+    QbaError = sub("_lib").QbaError
+    n, nd, sizeL, inst, base = 7, 2, 70, 37, 99
+    words = 4 + 5 * (n + 1)
+    fill = 0x5A5A5A5A
+    want, lists = tables_rows(engine, n, nd, base, inst, sizeL, keep_lists=True)
+
+    def sampled(o=None):
+        return engine.montecarlo_sampled(n, nd, base, inst, sizeL, out=o)
+
+    def from_lists(o=None):
+        return engine.montecarlo_lists(n, nd, base, lists, sizeL, out=o)
+
+    new = lambda *shape, dtype=torch.int32, device=engine.device: \
+        torch.zeros(shape, dtype=dtype, device=device)  # noqa: E731
+    for run in (sampled, from_lists):
+        out = torch.full((inst, words), fill, dtype=torch.int32, device=engine.device)
+        ret = run(out)
+        assert ret.data_ptr() == out.data_ptr()
+        rows = out.cpu().numpy()
+        assert not np.any(rows == fill)
+        _eq(rows, want)
+        for bad in (new(inst, words, dtype=torch.int64), new(inst, words, dtype=torch.float32),
+                    new(inst + 1, words), new(inst, words + 1), new(inst * words),
+                    new(inst, words, device="cpu"), new(inst, 2 * words)[:, ::2], new(words, inst).t()):
+            with pytest.raises(QbaError):
+                run(bad)
+        _eq(run().cpu().numpy(), want)  # and the engine still works
+    for bad in (lists.cpu(), lists.to(torch.int32), lists[:, :-1], lists[:, :, :sizeL - 1], lists[0]):
+        with pytest.raises(QbaError):
+            engine.montecarlo_lists(n, nd, base, bad, sizeL)
+    with pytest.raises(QbaError):
+        engine.montecarlo_sampled(n, n + 1, base, inst, sizeL)
+    with pytest.raises(QbaError):
+        engine.montecarlo_sampled(n, nd, base, inst, 1 << 31)
+
+
+def test_batches_split_points_and_streams(engine):
+    import torch
+    mc = sub("montecarlo")
+    n, nd, sizeL, seed = 7, 2, 50, 31337
+    fused = mc.run(n, sizeL, nd, 300, seed, engine, batch=128, path="fused")
+    assert fused == mc.run(n, sizeL, nd, 300, seed, engine, batch=128) and fused["runs"] == 300
+    assert fused == mc.run(n, sizeL, nd, 300, seed, engine, batch=4096, path="fused")
+    whole = engine.montecarlo_sampled(n, nd, seed, GRID_INST, sizeL).cpu().numpy()
+    parts = [engine.montecarlo_sampled(n, nd, seed + a, b - a, sizeL) for a, b in ((0, 29), (29, GRID_INST))]
+    _eq(torch.cat(parts).cpu().numpy(), whole)
+    _eq(engine.montecarlo_sampled(n, nd, seed + 5, 1, sizeL).cpu().numpy(), whole[5:6])
+    assert tuple(engine.montecarlo_sampled(n, nd, seed, 0, sizeL).shape) == (0, 4 + 5 * (n + 1))
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        again = engine.montecarlo_sampled(n, nd, seed, GRID_INST, sizeL)
+    side.synchronize()
+    _eq(again.cpu().numpy(), whole)
+
+
+def test_cli_fused_prints_the_same_summary():
+    env = dict(os.environ)
+    env["PYTHONPATH"] = str(ROOT) + os.pathsep + env.get("PYTHONPATH", "")
+    lines = []
+    for extra in ([], ["--fused"]):
+        cmd = [sys.executable, "-m", "tfg---quantum-byzantine-agreement_amd.tfg", "50", "2", "--parties", "7",
+               "--runs", "300", "--seed", "2024"] + extra
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=str(ROOT))
+        assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-1500:]
+        hits = [l for l in out.stdout.splitlines() if l.startswith("Runs:")]
+        assert len(hits) == 1
+        lines.append(hits[0])
+    assert lines[0] == lines[1] and "Runs: 300 Successes:" in lines[0]

@@ -103,6 +103,7 @@ __device__ __forceinline__ QbaU4 qba_philox(uint32_t c0, uint32_t c1, uint32_t c
 #define QBA_PROTO_RNG_CAP 64      // words one randint may draw; extra draws of `while v2 == v1`
 #define QBA_PROTO_ST_MAILBOX 1u   // status bit 0: a (dest, src) mailbox was full
 #define QBA_PROTO_ST_RNG 2u       // status bit 1: an RNG retry cap was hit
+#define QBA_PROTO_ST_RANGE 4u     // status bit 2: a list value >= w at a Q-correlated position (qba_montecarlo_lists)
 
 struct QbaFactor {
   int32_t bits;
@@ -251,6 +252,8 @@ int qba_ensure_staging(qba_ctx *ctx, size_t host_bytes, size_t dev_bytes);
 #define QBA_ZC_MAX (1u << 20)
 int qba_ensure_zc(qba_ctx *ctx, size_t bytes);
 int qba_set_device(qba_ctx *ctx);
+// The argument envelope of qba_montecarlo_sampled / _lists (qba_proto.hip)
+int qba_mc_check(const char *who, qba_ctx *ctx, int n, int n_dis, int64_t n_inst, uint64_t count, const void *out);
 
 static inline int qba_nq(int n) {  // ceil(log2(n+1)), tfg.py:317
   int q = 0;

@@ -33,6 +33,17 @@ struct QbaBatch {
   int packed;  // nibble rows: ld / inst_stride in bytes of packed rows
 };
 
+// qba_montecarlo_sampled (qba_mc_kern.h); fields have the kernel arguments' types
+struct QbaMc {
+  const QbaProgramSet *ps;
+  uint64_t seed_base;
+  int64_t n_inst;
+  uint64_t count;
+  int n_dis;
+  int32_t *out;
+  hipStream_t stream;
+};
+
 template <int NP>
 int qba_launch_lists(qba_ctx *ctx, const QbaLaunch &L);
 // Launch the pending deferred reduction (if any) on its stream; a later launch
@@ -40,6 +51,10 @@ int qba_launch_lists(qba_ctx *ctx, const QbaLaunch &L);
 int qba_flush_pending(qba_ctx *ctx, hipStream_t next);
 template <int NP>
 int qba_launch_batched(qba_ctx *ctx, const QbaBatch &B);
+template <int NP>
+int qba_launch_mc(qba_ctx *ctx, const QbaMc &M);
+template <int NP>
+void qba_mc_shape_n(int *waves, int64_t *lds, int *wgs);
 // QBA_BUILD_EXPERIMENT_FLAGS of the per-n object (qba_build_flags ORs them)
 template <int NP>
 int qba_lists_build_flags();

@@ -91,6 +91,26 @@ extern "C" int qba_sample_check_batched_packed(qba_ctx *ctx, int n, uint64_t see
                  "qba_sample_check_batched_packed");
 }
 
+extern "C" int qba_montecarlo_sampled(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
+                                      uint64_t count, int32_t *out, qba_stream stream) {
+  int rc = qba_mc_check("qba_montecarlo_sampled", ctx, n, n_dis, n_inst, count, out);
+  if (rc) return rc;
+  if ((rc = need_program(ctx, n, "qba_montecarlo_sampled"))) return rc;
+  if (n_inst == 0) return QBA_OK;
+  if ((rc = qba_set_device(ctx))) return rc;
+  QbaMc M{(const QbaProgramSet *)ctx->prog_dev[n], seed_base, n_inst, count, n_dis, out, (hipStream_t)stream};
+  return with_n(n, [&](auto k) { return qba_launch_mc<decltype(k)::value>(ctx, M); });
+}
+
+extern "C" int qba_montecarlo_shape(int n, int *waves, int64_t *lds_bytes, int *wgs_per_cu) {
+  if (n < 1 || n > QBA_MAX_PARTIES || !waves || !lds_bytes || !wgs_per_cu)
+    return qba_fail(QBA_EINVAL, "qba_montecarlo_shape: n_parties must be in [1, 15] and the outputs not NULL");
+  return with_n(n, [&](auto k) {
+    qba_mc_shape_n<decltype(k)::value>(waves, lds_bytes, wgs_per_cu);
+    return (int)QBA_OK;
+  });
+}
+
 // Launches of at most QBA_CHUNK entries (32-bit in-kernel offsets, u32 bins)
 // that never cross a multiple of 2^33 entries (inside a launch the high word
 // of the Philox pair counter e >> 1 is constant: qba_sample_quad keeps it in

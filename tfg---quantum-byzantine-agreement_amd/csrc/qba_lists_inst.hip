@@ -2,6 +2,7 @@
 // n = 1..15 with -DQBA_INST_N=n (csrc/Makefile), in parallel.
 #include "qba_lists_kern.h"
 #include "qba_lists_launch.h"
+#include "qba_mc_kern.h"
 
 #ifndef QBA_INST_N
 #error "build with -DQBA_INST_N=<n>"
@@ -9,4 +10,6 @@
 
 template int qba_launch_lists<QBA_INST_N>(qba_ctx *ctx, const QbaLaunch &L);
 template int qba_launch_batched<QBA_INST_N>(qba_ctx *ctx, const QbaBatch &B);
+template int qba_launch_mc<QBA_INST_N>(qba_ctx *ctx, const QbaMc &M);
+template void qba_mc_shape_n<QBA_INST_N>(int *waves, int64_t *lds, int *wgs);
 template <> int qba_lists_build_flags<QBA_INST_N>() { return QBA_BUILD_EXPERIMENT_FLAGS; }

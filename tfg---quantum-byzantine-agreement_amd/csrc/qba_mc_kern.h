@@ -1,0 +1,173 @@
+// qba_mc_kern.h -- the fused Monte-Carlo kernel (qba_montecarlo_sampled): a
+// wavefront samples the entries of one instance, distils them into the masks
+// the protocol rounds consult (mc_entry, qba_proto_rounds.h), runs the rounds
+// and writes the instance's result row.  No list, no histogram and no int64
+// table leaves the CU.  Included after the list kernels by qba_lists_inst.hip,
+// once per n.  DESIGN.md section 13.
+//
+// The entries are those of qba_k_batched, bit for bit: instance i draws entry
+// e of [0, count) with Philox key seed_base + i (qba_entry_d; the closed-form
+// sampler takes a pair's two entries from its one block, as qba_sample_quad).
+//
+// LDS of a workgroup: the sampler's tables, staged once (qba_stage) and shared
+// by its waves, then per wave a ProtoShared and the mailbox.  The waves are
+// independent after the staging barrier (proto_sync<false>): wave v of
+// workgroup b owns instances b * waves + v, + gridDim.x * waves, ..., so a
+// ragged last group of instances just leaves some waves with one trip fewer.
+#pragma once
+#include "qba_lists_launch.h"
+#include "qba_proto_rounds.h"
+
+constexpr size_t QBA_MC_CU_LDS = 160 * 1024;  // LDS of a CU, and the most one workgroup may take
+constexpr int QBA_MC_CU_WAVES = 16;           // resident waves per CU the shapes are chosen for (<= 128 VGPRs)
+
+struct QbaMcShape {
+  int waves;   // per workgroup; 0: the tables leave no room for a wave
+  size_t lds;  // dynamic LDS bytes of a workgroup
+  int wgs;     // workgroups a CU holds
+};
+
+__host__ __device__ constexpr size_t qba_mc_wave_lds(int G, int w) {
+  return (size_t)(PROTO_S_WORDS + ((proto_box_words(G, w) + 3) & ~3)) * sizeof(uint32_t);
+}
+
+// Waves per workgroup, at most max_waves: the count that keeps the most waves
+// resident on a CU (up to QBA_MC_CU_WAVES); among equals the largest, which
+// stages the fewest copies of the tables.
+__host__ __device__ constexpr QbaMcShape qba_mc_shape(size_t tables, int G, int w, int max_waves) {
+  QbaMcShape best{0, 0, 0};
+  int best_res = 0;
+  for (int nw = 1; nw <= max_waves; ++nw) {
+    const size_t lds = tables + (size_t)nw * qba_mc_wave_lds(G, w);
+    if (lds > QBA_MC_CU_LDS) break;
+    int wgs = (int)(QBA_MC_CU_LDS / lds);
+    const int by_waves = QBA_MC_CU_WAVES / nw > 1 ? QBA_MC_CU_WAVES / nw : 1;
+    if (wgs > by_waves) wgs = by_waves;
+    const int res = wgs * nw;
+    if (res >= best_res) {
+      best_res = res;
+      best = QbaMcShape{nw, lds, wgs};
+    }
+  }
+  return best;
+}
+
+// Table bytes the per-n wave count is compiled for: the closed-form stage
+// tables, else the canonical program's (uniform byte factors).  A program with
+// larger tables runs fewer waves of the same kernel (qba_launch_mc).
+template <int NP, int SAMP>
+constexpr size_t qba_mc_tables() {
+  using C = QCfg<NP>;
+  if (SAMP == QBA_S_CLOSED) return (size_t)((CF<NP>::WORDS + 3) & ~3) * sizeof(uint32_t);
+  return (size_t)((C::NFB * 256 + C::W + 1) & ~1) * sizeof(uint64_t);
+}
+template <int NP, int SAMP>
+constexpr int qba_mc_waves() {
+  return qba_mc_shape(qba_mc_tables<NP, SAMP>(), QCfg<NP>::G, QCfg<NP>::W, 16).waves;
+}
+
+template <int NP, int SAMP, int NW>
+__global__ void __attribute__((amdgpu_flat_work_group_size(64, NW * 64)))
+    qba_k_mc_sampled(const QbaProgramSet *__restrict__ ps, uint64_t seed_base, int64_t n_inst, uint32_t count,
+                     int n_dis, int nw_run, int32_t *__restrict__ out) {
+  using C = QCfg<NP>;
+  constexpr int ND = CF<NP>::ND;
+  extern __shared__ __align__(16) uint64_t lds[];
+  const uint64_t *pat, *apat, *thr;
+  const uint32_t *pl;
+  uint32_t *waves = qba_stage<NP, 1, SAMP, NW * 64>(ps, lds, pat, apat, thr, pl);
+  __syncthreads();
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = (int)__lane_id();
+  if (wv >= nw_run) return;  // tables larger than the shape was compiled for: fewer waves have room
+  uint32_t *mine = waves + (size_t)wv * (qba_mc_wave_lds(C::G, C::W) / sizeof(uint32_t));
+  ProtoShared &S = *reinterpret_cast<ProtoShared *>(mine);
+  uint32_t *box = mine + PROTO_S_WORDS;
+  const int64_t stride = (int64_t)gridDim.x * nw_run;
+  for (int64_t inst = (int64_t)blockIdx.x * nw_run + wv; inst < n_inst; inst += stride) {
+    const uint64_t key = seed_base + (uint64_t)inst;
+    const uint32_t k0 = __builtin_amdgcn_readfirstlane((uint32_t)key);
+    const uint32_t k1 = __builtin_amdgcn_readfirstlane((uint32_t)(key >> 32));
+    proto_sync<false>();  // the previous instance's row stores have read S
+    mc_begin(S, box, C::G, C::W, lane);
+    proto_sync<false>();
+    uint32_t seen = 0, bad = 0;
+    if constexpr (SAMP == QBA_S_CLOSED) {
+      // lane l takes pairs l, l + 64, ...: one Philox block, two entries (the
+      // second half of the last block of an odd count stays unused)
+      const uint32_t npair = (count + 1u) >> 1;
+      for (uint32_t p = (uint32_t)lane; p < npair; p += 64u) {
+        const QbaU4 x = qba_philox(p, 0u, 0u, 0u, k0, k1);
+#pragma unroll
+        for (uint32_t h = 0; h < 2; ++h) {
+          if (2u * p + h >= count) break;
+          uint32_t d[ND], D[4] = {0u, 0u, 0u, 0u};
+          qba_closed_half<NP>(h ? x.z : x.x, h ? x.w : x.y, (uint64_t)p, h, k0, k1, pl, d);
+#pragma unroll
+          for (int i = 0; i < ND; ++i) D[i] = d[i];
+          mc_entry<false>(S, box, D, C::G, C::W, seen, bad);
+        }
+      }
+    } else {
+      for (uint32_t e = (uint32_t)lane; e < count; e += 64u) {
+        uint32_t d[ND], D[4] = {0u, 0u, 0u, 0u};
+        qba_entry_d<NP, SAMP>((uint64_t)e, k0, k1, ps, pat, apat, thr, pl, d);
+#pragma unroll
+        for (int i = 0; i < ND; ++i) D[i] = d[i];
+        mc_entry<false>(S, box, D, C::G, C::W, seen, bad);
+      }
+    }
+    mc_flags(box, C::G, C::W, seen, bad);
+    proto_sync<false>();
+    uint32_t st;
+    const uint32_t pnz = mc_finish<false>(S, box, C::G, C::W, lane, st);
+    proto_sync<false>();
+    proto_rounds<false>(S, box, NP, n_dis, key, pnz, st, lane, out + inst * (int64_t)(4 + 5 * C::G));
+  }
+}
+
+// The launch of one sampler's kernel: full workgroups of its compiled wave
+// count, of which nw_run work; persistent over the instances.
+template <int NP, int SAMP>
+static int qba_launch_mc_s(qba_ctx *ctx, const QbaMc &M, size_t tables) {
+  using C = QCfg<NP>;
+  constexpr int NW = qba_mc_waves<NP, SAMP>();
+  static_assert(NW >= 1, "no room for a wave beside the tables");
+  const QbaMcShape sh = qba_mc_shape(tables, C::G, C::W, NW);
+  if (sh.waves < 1) return qba_fail(QBA_EUNSUPPORTED, "qba_montecarlo_sampled: the program's tables leave no LDS for a wave");
+  const void *kern = (const void *)qba_k_mc_sampled<NP, SAMP, NW>;
+  if (int rc = lds_allow(kern, sh.lds)) return rc;
+  const int64_t need = (M.n_inst + sh.waves - 1) / sh.waves, cap = (int64_t)ctx->num_cus * sh.wgs;
+  const int grid = (int)(need < cap ? need : cap);
+  const uint32_t count = (uint32_t)M.count;
+  const int nw_run = sh.waves;
+  const void *args[] = {&M.ps, &M.seed_base, &M.n_inst, &count, &M.n_dis, &nw_run, &M.out};
+  QBA_HIP(hipLaunchKernel(kern, dim3(grid), dim3(NW * 64), const_cast<void **>(args), sh.lds, M.stream));
+  QBA_HIP(hipGetLastError());
+  return QBA_OK;
+}
+
+template <int NP>
+int qba_launch_mc(qba_ctx *ctx, const QbaMc &M) {
+  const QbaProgramSet *hs = reinterpret_cast<const QbaProgramSet *>(ctx->prog_host[NP]);
+  const int samp = sampler_of<NP>(hs);  // as qba_launch_batched chooses it
+  if (int rc = check_closed<NP>(hs)) return rc;
+  const size_t tables = table_lds<NP>(hs, samp);
+  if (samp == QBA_S_CLOSED) {
+    if constexpr (NP <= QBA_CLOSED_MAX_N) return qba_launch_mc_s<NP, QBA_S_CLOSED>(ctx, M, tables);
+    return qba_fail(QBA_EUNSUPPORTED, "closed form beyond n = 11");
+  }
+  if (samp == QBA_S_FAST) return qba_launch_mc_s<NP, QBA_S_FAST>(ctx, M, tables);
+  return qba_launch_mc_s<NP, QBA_S_GENERAL>(ctx, M, tables);
+}
+
+// The shape of the shipped programs' kernel (closed form up to n = 11, the
+// canonical tables above): qba_montecarlo_shape
+template <int NP>
+void qba_mc_shape_n(int *waves, int64_t *lds, int *wgs) {
+  constexpr int SAMP = NP <= QBA_CLOSED_MAX_N ? QBA_S_CLOSED : QBA_S_FAST;
+  constexpr QbaMcShape sh = qba_mc_shape(qba_mc_tables<NP, SAMP>(), QCfg<NP>::G, QCfg<NP>::W, 16);
+  *waves = sh.waves;
+  *lds = (int64_t)sh.lds;
+  *wgs = sh.wgs;
+}

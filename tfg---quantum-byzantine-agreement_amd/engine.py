@@ -279,6 +279,60 @@ class Engine:
              _ptr(counts.P), _ptr(out), self.stream())
         return out
 
+    def _rows_out(self, n: int, n_inst: int, out: Optional[torch.Tensor]) -> torch.Tensor:
+        words = 4 + 5 * (n + 1)
+        if out is None:
+            out = torch.empty((n_inst, words), dtype=torch.int32, device=self.device)
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != (n_inst, words) or \
+                not out.is_contiguous() or out.device != self.device:
+            raise QbaError(f"out must be a contiguous int32 [{n_inst}, {words}] device tensor")
+        return out
+
+    @staticmethod
+    def _check_mc(n: int, n_dishonest: int, n_inst: int, count: int) -> None:
+        if not 0 <= n_dishonest <= n:
+            raise QbaError(f"n_dishonest={n_dishonest} outside [0, {n}]")
+        if n_inst < 0 or not 0 <= count < 1 << 31:
+            raise QbaError("n_inst >= 0 and 0 <= count < 2^31")
+
+    def montecarlo_sampled(self, n: int, n_dishonest: int, seed_base: int, n_inst: int, count: int,
+                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """n_inst instances (key seed_base + i) of `count` entries sampled,
+        distilled and decided in one kernel (qba_montecarlo_sampled): the rows
+        of protocol_batched(sample_check_batched(...)), int32
+        [n_inst, 4 + 5*(n+1)], with no list buffer and no count tables."""
+        self._check_n(n)
+        self._check_mc(n, n_dishonest, n_inst, count)
+        self.prepare(n)
+        out = self._rows_out(n, n_inst, out)
+        call("qba_montecarlo_sampled", self.ctx, n, n_dishonest, int(seed_base) & ((1 << 64) - 1), n_inst, count,
+             _ptr(out), self.stream())
+        return out
+
+    def montecarlo_lists(self, n: int, n_dishonest: int, seed_base: int, lists, count: int,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The same rows from injected lists (qba_montecarlo_lists): a uint8
+        [n_inst, n+1, >= count] device tensor in the layout of
+        sample_check_batched, or a host array of that shape (copied to the
+        device).  A row's status 4 marks a value >= w at a Q-correlated
+        position (montecarlo.ST_RANGE)."""
+        self._check_n(n)
+        if isinstance(lists, np.ndarray):
+            lists = torch.from_numpy(np.array(lists, dtype=np.uint8, order="C")).to(self.device)  # a writable copy
+        if not isinstance(lists, torch.Tensor) or lists.dtype != torch.uint8 or lists.dim() != 3 or \
+                lists.shape[1] != n + 1 or lists.device != self.device or \
+                (lists.numel() and lists.stride(2) != 1) or lists.shape[2] < count:
+            raise QbaError("lists must be a uint8 [n_inst, n+1, >= count] device tensor with unit column stride")
+        n_inst = lists.shape[0]
+        self._check_mc(n, n_dishonest, n_inst, count)
+        ld, stride = (lists.stride(1), lists.stride(0)) if lists.numel() else (count, (n + 1) * count)
+        if count and n_inst and (ld < count or (n_inst > 1 and stride < (n + 1) * ld)):
+            raise QbaError("lists rows overlap: need stride(1) >= count and stride(0) >= (n+1)*stride(1)")
+        out = self._rows_out(n, n_inst, out)
+        call("qba_montecarlo_lists", self.ctx, n, n_dishonest, int(seed_base) & ((1 << 64) - 1), n_inst, count,
+             _ptr(lists), ld, stride, _ptr(out), self.stream())
+        return out
+
     # -- (A5-A8) count mode -------------------------------------------------------
     def check_counts(self, lists: torch.Tensor, n: int, count: int,
                      counts: Optional[Counts] = None, accumulate: bool = False) -> Counts:

@@ -17,8 +17,15 @@ Result row of one instance (int32, ``out_words(n)`` = 4 + 5*(n+1) words):
 ``{success, dishonest-rank bitmask, empty-V_i rank bitmask, status}`` then per
 rank r = 0..n ``{decision (-1 on an empty V_i), V_r bitmask, accept, reject,
 sent}`` (rank 0: zeros; the commander keeps no V).  status bit 0 = mailbox
-overflow (device only), bit 1 = an RNG retry cap was hit; with a nonzero status
-every other field is 0.
+overflow (device only), bit 1 = an RNG retry cap was hit, bit 2 = a list value
+>= w at a Q-correlated position (``Engine.montecarlo_lists`` only); with a
+nonzero status every other field is 0.
+
+The fused path (``run(path="fused")``, ``Engine.montecarlo_sampled`` /
+``montecarlo_lists``) goes from lists to rows in one kernel.  It rests on the
+fact that the rounds consult only bitwise reductions over an instance's
+Q-correlated entries, restated on the host by :func:`masks_from_lists` and
+:func:`masks_from_tables`.
 """
 from __future__ import annotations
 
@@ -33,7 +40,7 @@ from .countmode import CountParty
 MASK64 = (1 << 64) - 1
 CTR_TAG = 0x51424150  # word 3 of every protocol counter; the sampler's is 0 or 1
 RNG_CAP = 64          # words one randint may draw
-ST_MAILBOX, ST_RNG = 1, 2
+ST_MAILBOX, ST_RNG, ST_RANGE = 1, 2, 4
 
 _M0, _M1 = 0xD2511F53, 0xCD9E8D57
 _W0, _W1 = 0x9E3779B9, 0xBB67AE85
@@ -183,19 +190,93 @@ def summarize(n: int, out: np.ndarray) -> dict:
             "decisions": {int(v): int(c) for v, c in zip(vals, cnt)}}
 
 
+def _nq(n: int) -> int:
+    return int(n).bit_length()  # ceil(log2(n + 1)), tfg.py:317
+
+
+def masks_from_tables(n: int, flat) -> dict:
+    """What the protocol keeps of an instance's count tables ``flat`` = [H | C
+    | P] (``count_tables``), as qba_k_protocol's prologue distils it:
+
+    ``pnz``   int, bit u: P[u] != 0
+    ``hmask`` [w, n+1], bit x: H[u][g][x] != 0
+    ``czero`` [w, n+1], bit h: C[u][g][h] == 0
+    ``rep``   [w, n+1], min h with C[u][g][h] == P[u]
+    """
+    g, w = n + 1, 1 << _nq(n)
+    flat = np.asarray(flat)
+    h, c = w * g * w, w * g * g
+    H, C, P = flat[:h].reshape(w, g, w), flat[h:h + c].reshape(w, g, g), flat[h + c:h + c + w]
+    bits_w, bits_g = 1 << np.arange(w, dtype=np.int64), 1 << np.arange(g, dtype=np.int64)
+    return {"pnz": int(((P != 0) * bits_w).sum()),
+            "hmask": ((H != 0) * bits_w).sum(axis=2),
+            "czero": ((C == 0) * bits_g).sum(axis=2),
+            "rep": np.argmax(C == P[:, None, None], axis=2)}  # the diagonal is |P_u|: a hit always exists
+
+
+def masks_from_lists(n: int, lists) -> dict:
+    """The same four, straight from the lists [n+1, sizeL] with no counter: each
+    is a bitwise reduction over the Q-correlated entries (L0 != L1) of P_u,
+    u = L1.  With E(g) = the entry's equal-pair mask {h : L_h == L_g}:
+
+    =================================  =========================================
+    the tables give                    over the entries of P_u it is
+    =================================  =========================================
+    P[u] != 0                          OR of "an entry with this u exists"
+    x with H[u][g][x] != 0             OR of 1 << L_g
+    h with C[u][g][h] == 0             complement of OR of E(g)
+    rep(u, g)                          lowest bit of AND of E(g) (all ones for
+                                       an empty P_u: rep = 0)
+    =================================  =========================================
+
+    This is what the fused kernels compute in LDS (csrc/qba_proto_rounds.h).
+    Values >= w at a Q-correlated position are an error (ST_RANGE there,
+    ValueError here), as in ``Engine.count_tables``."""
+    g, w = n + 1, 1 << _nq(n)
+    L = np.asarray(lists, dtype=np.int64).reshape(g, -1)
+    q = L[:, L[0] != L[1]]
+    if q.size and q.max() >= w:
+        raise ValueError("lists hold values >= w at Q-correlated positions")
+    pnz = 0
+    hmask = np.zeros((w, g), np.int64)
+    eq_or = np.zeros((w, g), np.int64)
+    eq_and = np.full((w, g), -1, np.int64)
+    bits_g = 1 << np.arange(g, dtype=np.int64)
+    for k in range(q.shape[1]):
+        e = q[:, k]
+        u = int(e[1])
+        E = ((e[:, None] == e[None, :]) * bits_g).sum(axis=1)  # E(g), bit h
+        pnz |= 1 << u
+        hmask[u] |= 1 << e
+        eq_or[u] |= E
+        eq_and[u] &= E
+    return {"pnz": pnz, "hmask": hmask, "czero": ~eq_or & ((1 << g) - 1),
+            "rep": np.array([[(int(a) & -int(a)).bit_length() - 1 for a in row] for row in eq_and])}
+
+
 def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, packed: bool = True,
-        batch: int = 4096) -> dict:
-    """``runs`` independent instances on the device, ``batch`` at a time:
-    sample_check_batched then protocol_batched with key ``seed + offset``; the
-    list buffer is reused across batches and only the result rows are copied
-    to the host.  Returns :func:`summarize` of all rows."""
+        batch: int = 4096, path: str = "tables") -> dict:
+    """``runs`` independent instances on the device, ``batch`` at a time, batch
+    at offset ``off`` under key ``seed + off``; only the result rows are copied
+    to the host.  Returns :func:`summarize` of all rows.
+
+    ``path="tables"`` (the default): sample_check_batched then
+    protocol_batched; the list buffer is reused across batches.
+    ``path="fused"``: one montecarlo_sampled call per batch -- the same
+    instances and rows, with no list buffer and no count tables (``packed``
+    has nothing to apply to)."""
     import torch
     if runs < 0 or batch < 1:
         raise ValueError("runs >= 0 and batch >= 1")
+    if path not in ("tables", "fused"):
+        raise ValueError("path is 'tables' or 'fused'")
     lists, outs = None, []
     for off in range(0, runs, batch):
         b = min(batch, runs - off)
         key = (int(seed) + off) & MASK64
+        if path == "fused":
+            outs.append(engine.montecarlo_sampled(n, n_dishonest, key, b, sizeL))
+            continue
         buf, counts = engine.sample_check_batched(n, key, b, sizeL, None if lists is None else lists[:b],
                                                   packed=packed)
         if lists is None:

@@ -55,6 +55,9 @@ def _args(argv):
                     help="in-process: this many independent count-mode instances, lists, rounds and decisions "
                          "on the device (montecarlo.run); prints runs, successes and the success rate")
     ap.add_argument("--batch", type=int, default=4096, help="instances per device batch of --runs")
+    ap.add_argument("--fused", action="store_true",
+                    help="with --runs: sample, distil and decide each batch in one kernel, with no list buffer and "
+                         "no count tables (montecarlo.run path='fused'); the same instances and summary")
     ap.add_argument("--quiet", action="store_true", help="print only the outcome")
     ap.add_argument("--timing", action="store_true", help="print the wall time of the run")
     ap.add_argument("--wire", action="store_true",
@@ -178,7 +181,8 @@ def _montecarlo(a, eng, size_l) -> int:
     from . import montecarlo
     seed = secrets.randbits(62) if a.seed is None else a.seed
     t0 = time.perf_counter()
-    s = montecarlo.run(a.parties, size_l, a.nDishonest, a.runs, seed, eng, batch=a.batch)
+    s = montecarlo.run(a.parties, size_l, a.nDishonest, a.runs, seed, eng, batch=a.batch,
+                       path="fused" if a.fused else "tables")
     print(f"Runs: {s['runs']} Successes: {s['successes']} Rate: {s['rate']:.6f} "
           f"(n={a.parties}, sizeL={size_l}, dishonest={a.nDishonest}, empty-V_i runs={s['empty_vi_runs']})")
     if a.timing:

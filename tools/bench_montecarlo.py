@@ -8,7 +8,13 @@ instances x n = 7 x sizeL = 1e5, 2 dishonest, on one GPU.
       (CountParty under run_local, one instance at a time, on the GPU engine)
       over --host-instances instances, scaled to 4096 -- EXTRAPOLATED.
 
-(a) and (b) are device-event times of single calls on warm code: median, min
+  (d) montecarlo_sampled: the fused path, lists to rows in one kernel with no
+      list buffer and no tables -- the same rows as (a) + (b), which is
+      checked; "a_plus_b" times (a) then (b) as one interval for comparison.
+      --sizeL may be given several times (the fused path is meant for small
+      ones); --host-instances 0 skips (c).
+
+(a), (b) and (d) are device-event times of single calls on warm code: median, min
 and max over --repeats launches after --warmup launches.  (c) is host wall
 time around runs that end in device synchronisation (each reads its tables
 back).  Prints one JSON line; --out also writes it to a file.  No GPU: fails.
@@ -45,7 +51,7 @@ def _events(fn, warmup, repeats):
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--parties", type=int, default=7)
-    ap.add_argument("--sizeL", type=int, default=100_000)
+    ap.add_argument("--sizeL", type=int, action="append", default=None, help="default 100000; repeatable")
     ap.add_argument("--dishonest", type=int, default=2)
     ap.add_argument("--instances", type=int, default=4096)
     ap.add_argument("--host-instances", type=int, default=64)
@@ -55,10 +61,21 @@ def main(argv=None) -> int:
     ap.add_argument("--out", type=Path, default=None)
     a = ap.parse_args(argv)
 
-    import torch
     eng = importlib.import_module(f"{PKG}.engine").Engine(0)
+    lines = [json.dumps(_measure(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
+    print("\n".join(lines))
+    if a.out is not None:
+        a.out.parent.mkdir(parents=True, exist_ok=True)
+        a.out.write_text("\n".join(lines) + "\n")
+    eng.close()
+    return 0
+
+
+def _measure(a, eng, size_l) -> dict:
+    import torch
     mc = importlib.import_module(f"{PKG}.montecarlo")
     n, nd, inst = a.parties, a.dishonest, a.instances
+    a = argparse.Namespace(**{**vars(a), "sizeL": size_l})
     lists, counts = eng.sample_check_batched(n, a.seed, inst, a.sizeL, packed=True)
     out = eng.protocol_batched(n, nd, a.seed, counts)
     torch.cuda.synchronize()
@@ -75,7 +92,22 @@ def main(argv=None) -> int:
     summary = mc.summarize(n, out.cpu().numpy())
     res["result"] = {k: summary[k] for k in ("runs", "successes", "rate", "empty_vi_runs")}
 
+    def both():
+        eng.sample_check_batched(n, a.seed, inst, a.sizeL, lists, packed=True)
+        eng.protocol_batched(n, nd, a.seed, counts, out)
+
+    res["a_plus_b"] = _events(both, a.warmup, a.repeats)
+    fused = eng.montecarlo_sampled(n, nd, a.seed, inst, a.sizeL)
+    res["d_montecarlo_sampled"] = _events(lambda: eng.montecarlo_sampled(n, nd, a.seed, inst, a.sizeL, fused),
+                                          a.warmup, a.repeats)
+    res["d_montecarlo_sampled"]["rows_equal_tables_path"] = bool(torch.equal(fused, out))
+    # faster only where the min-max ranges do not overlap
+    res["d_faster_than_a_plus_b"] = res["d_montecarlo_sampled"]["max_ms"] < res["a_plus_b"]["min_ms"]
+    res["a_plus_b_faster_than_d"] = res["a_plus_b"]["max_ms"] < res["d_montecarlo_sampled"]["min_ms"]
+
     k = a.host_instances
+    if k <= 0:
+        return res
     mc.run_host(n, a.sizeL, nd, 2, a.seed, eng)  # warm
     t0 = time.perf_counter()
     host = mc.run_host(n, a.sizeL, nd, k, a.seed, eng)
@@ -85,13 +117,7 @@ def main(argv=None) -> int:
                                     "extrapolated_s": wall / k * inst, "extrapolated": True,
                                     "rows_equal_kernel": bool((host == out[:k].cpu().numpy()).all())}
     res["b_below_a"] = res["b_protocol_batched"]["median_ms"] < res["a_sample_check_batched_packed"]["median_ms"]
-    line = json.dumps(res)
-    print(line)
-    if a.out is not None:
-        a.out.parent.mkdir(parents=True, exist_ok=True)
-        a.out.write_text(line + "\n")
-    eng.close()
-    return 0
+    return res
 
 
 if __name__ == "__main__":
