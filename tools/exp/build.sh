@@ -6,9 +6,11 @@
 #   PROBES=1   apply tools/exp/probes.patch to a copy first: the attribution
 #              probes (-DQBA_EXP_NOSTORE, _NOATOMIC, _NOCOND3, _CHEAPRNG, _TIMING,
 #              ...) and the switches of the rejected variants, as of round 5.
-#              (Its host hunks predate the launchers' move to
-#              qba_lists_launch.h: use it with SRC= on an export of such a
-#              revision, or re-point those five hunks first.)
+#              (The patch is stale against the working tree: its host hunks
+#              predate the launchers' move to qba_lists_launch.h and its
+#              kernel hunks the split of qba_lists_kern.h into
+#              qba_lists_sample.h / _count.h / _step.h.  Use it with SRC= on
+#              an export of a revision from before both.)
 set -e
 here="$(cd "$(dirname "$0")/../../tfg---quantum-byzantine-agreement_amd/csrc" && pwd)"
 src=${SRC:-$here}
