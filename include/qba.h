@@ -292,6 +292,38 @@ QBA_API int qba_montecarlo_lists(qba_ctx *ctx, int n_parties, int n_dishonest, u
  * section 13).  Host only; ctx is not needed. */
 QBA_API int qba_montecarlo_shape(int n_parties, int *waves, int64_t *lds_bytes, int *wgs_per_cu);
 
+/* A whole sizeL curve in one pass: every instance decided at each of the
+ * checkpoints counts_host[0] < counts_host[1] < ... < counts_host[n_counts-1]
+ * < 2^31, 1 <= n_counts <= QBA_MC_CURVE_MAX (counts_host[0] may be 0).  The
+ * entries [0, c) of an instance are the first c of any larger count and the
+ * masks are monotone reductions over them, so one pass over [0, c_max) stops
+ * at each checkpoint, runs the rounds on the masks so far and writes a row:
+ * instance i at checkpoint j writes 4 + 5*(n+1) int32 at
+ *   out_dev + ((int64_t)j * n_instances + i) * (4 + 5*(n+1)),
+ * word for word (status included) the row of qba_montecarlo_sampled /
+ * qba_montecarlo_lists with count = counts_host[j].  In the lists form a
+ * value >= w at Q-correlated position k gives status 4 in exactly the
+ * checkpoints with counts_host[j] > k.
+ * n_parties, n_dishonest and then the checkpoint list (pointer not NULL,
+ * n_counts in range, strictly increasing, last < 2^31) are checked before
+ * ctx, else QBA_EINVAL; the lists form needs ld >= counts_host[n_counts-1].
+ * n_instances == 0 writes nothing.  The checkpoints travel by value in the
+ * kernel arguments: counts_host may be reused when the call returns.
+ * Asynchronous on `stream`, allocate and copy nothing, legal in a stream
+ * capture.  The sampled form needs both resource programs (QBA_ESTATE). */
+#define QBA_MC_CURVE_MAX 32
+QBA_API int qba_montecarlo_curve_sampled(qba_ctx *ctx, int n_parties, int n_dishonest, uint64_t seed_base,
+                                         int64_t n_instances, const uint32_t *counts_host, int n_counts,
+                                         int32_t *out_dev, qba_stream stream);
+QBA_API int qba_montecarlo_curve_lists(qba_ctx *ctx, int n_parties, int n_dishonest, uint64_t seed_base,
+                                       int64_t n_instances, const uint32_t *counts_host, int n_counts,
+                                       const uint8_t *lists_dev, uint64_t ld, uint64_t inst_stride,
+                                       int32_t *out_dev, qba_stream stream);
+/* The launch shape of qba_montecarlo_curve_sampled, as qba_montecarlo_shape:
+ * each wavefront also holds its running masks, 2*w*(n+1) + 2 words (DESIGN.md
+ * section 13.2), so some n run fewer wavefronts per workgroup. */
+QBA_API int qba_montecarlo_curve_shape(int n_parties, int *waves, int64_t *lds_bytes, int *wgs_per_cu);
+
 /* ---- (A5-A8) checks, exact-order mode (bit-exact protocol parity) --------------- */
 /* isQCorrList = {k : Li[k] != Lc[k]} (tfg.py:327) as ascending indices.
  * *count_host receives the number found; at most `cap` are written. Synchronous. */

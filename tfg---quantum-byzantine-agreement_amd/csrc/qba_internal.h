@@ -254,6 +254,15 @@ int qba_ensure_zc(qba_ctx *ctx, size_t bytes);
 int qba_set_device(qba_ctx *ctx);
 // The argument envelope of qba_montecarlo_sampled / _lists (qba_proto.hip)
 int qba_mc_check(const char *who, qba_ctx *ctx, int n, int n_dis, int64_t n_inst, uint64_t count, const void *out);
+// The checkpoints of a curve call, by value in the kernel arguments
+struct QbaMcCounts {
+  uint32_t c[QBA_MC_CURVE_MAX];
+  int n;
+};
+// The envelope of qba_montecarlo_curve_sampled / _lists: n_parties, n_dishonest
+// and the checkpoint list before ctx; fills `cv`
+int qba_mc_curve_check(const char *who, qba_ctx *ctx, int n, int n_dis, int64_t n_inst, const uint32_t *counts,
+                       int n_counts, const void *out, QbaMcCounts *cv);
 
 static inline int qba_nq(int n) {  // ceil(log2(n+1)), tfg.py:317
   int q = 0;

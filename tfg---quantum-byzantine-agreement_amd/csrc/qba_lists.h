@@ -44,6 +44,17 @@ struct QbaMc {
   hipStream_t stream;
 };
 
+// qba_montecarlo_curve_sampled (qba_mc_kern.h); as QbaMc
+struct QbaMcCurve {
+  const QbaProgramSet *ps;
+  uint64_t seed_base;
+  int64_t n_inst;
+  int n_dis;
+  int32_t *out;
+  hipStream_t stream;
+  QbaMcCounts counts;
+};
+
 template <int NP>
 int qba_launch_lists(qba_ctx *ctx, const QbaLaunch &L);
 // Launch the pending deferred reduction (if any) on its stream; a later launch
@@ -55,6 +66,10 @@ template <int NP>
 int qba_launch_mc(qba_ctx *ctx, const QbaMc &M);
 template <int NP>
 void qba_mc_shape_n(int *waves, int64_t *lds, int *wgs);
+template <int NP>
+int qba_launch_mc_curve(qba_ctx *ctx, const QbaMcCurve &M);
+template <int NP>
+void qba_mc_curve_shape_n(int *waves, int64_t *lds, int *wgs);
 // QBA_BUILD_EXPERIMENT_FLAGS of the per-n object (qba_build_flags ORs them)
 template <int NP>
 int qba_lists_build_flags();

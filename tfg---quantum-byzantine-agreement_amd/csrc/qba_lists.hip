@@ -102,6 +102,28 @@ extern "C" int qba_montecarlo_sampled(qba_ctx *ctx, int n, int n_dis, uint64_t s
   return with_n(n, [&](auto k) { return qba_launch_mc<decltype(k)::value>(ctx, M); });
 }
 
+extern "C" int qba_montecarlo_curve_sampled(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
+                                            const uint32_t *counts, int n_counts, int32_t *out,
+                                            qba_stream stream) {
+  QbaMcCurve M{nullptr, seed_base, n_inst, n_dis, out, (hipStream_t)stream, {}};
+  int rc = qba_mc_curve_check("qba_montecarlo_curve_sampled", ctx, n, n_dis, n_inst, counts, n_counts, out, &M.counts);
+  if (rc) return rc;
+  if ((rc = need_program(ctx, n, "qba_montecarlo_curve_sampled"))) return rc;
+  if (n_inst == 0) return QBA_OK;
+  if ((rc = qba_set_device(ctx))) return rc;
+  M.ps = (const QbaProgramSet *)ctx->prog_dev[n];
+  return with_n(n, [&](auto k) { return qba_launch_mc_curve<decltype(k)::value>(ctx, M); });
+}
+
+extern "C" int qba_montecarlo_curve_shape(int n, int *waves, int64_t *lds_bytes, int *wgs_per_cu) {
+  if (n < 1 || n > QBA_MAX_PARTIES || !waves || !lds_bytes || !wgs_per_cu)
+    return qba_fail(QBA_EINVAL, "qba_montecarlo_curve_shape: n_parties must be in [1, 15] and the outputs not NULL");
+  return with_n(n, [&](auto k) {
+    qba_mc_curve_shape_n<decltype(k)::value>(waves, lds_bytes, wgs_per_cu);
+    return (int)QBA_OK;
+  });
+}
+
 extern "C" int qba_montecarlo_shape(int n, int *waves, int64_t *lds_bytes, int *wgs_per_cu) {
   if (n < 1 || n > QBA_MAX_PARTIES || !waves || !lds_bytes || !wgs_per_cu)
     return qba_fail(QBA_EINVAL, "qba_montecarlo_shape: n_parties must be in [1, 15] and the outputs not NULL");

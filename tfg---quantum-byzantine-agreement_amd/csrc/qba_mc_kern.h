@@ -34,11 +34,13 @@ __host__ __device__ constexpr size_t qba_mc_wave_lds(int G, int w) {
 // Waves per workgroup, at most max_waves: the count that keeps the most waves
 // resident on a CU (up to QBA_MC_CU_WAVES); among equals the largest, which
 // stages the fewest copies of the tables.
-__host__ __device__ constexpr QbaMcShape qba_mc_shape(size_t tables, int G, int w, int max_waves) {
+// `extra`: bytes a wave holds beside its ProtoShared and mailbox (the curve
+// kernel's accumulator area)
+__host__ __device__ constexpr QbaMcShape qba_mc_shape(size_t tables, int G, int w, int max_waves, size_t extra = 0) {
   QbaMcShape best{0, 0, 0};
   int best_res = 0;
   for (int nw = 1; nw <= max_waves; ++nw) {
-    const size_t lds = tables + (size_t)nw * qba_mc_wave_lds(G, w);
+    const size_t lds = tables + (size_t)nw * (qba_mc_wave_lds(G, w) + extra);
     if (lds > QBA_MC_CU_LDS) break;
     int wgs = (int)(QBA_MC_CU_LDS / lds);
     const int by_waves = QBA_MC_CU_WAVES / nw > 1 ? QBA_MC_CU_WAVES / nw : 1;
@@ -167,6 +169,139 @@ template <int NP>
 void qba_mc_shape_n(int *waves, int64_t *lds, int *wgs) {
   constexpr int SAMP = NP <= QBA_CLOSED_MAX_N ? QBA_S_CLOSED : QBA_S_FAST;
   constexpr QbaMcShape sh = qba_mc_shape(qba_mc_tables<NP, SAMP>(), QCfg<NP>::G, QCfg<NP>::W, 16);
+  *waves = sh.waves;
+  *lds = (int64_t)sh.lds;
+  *wgs = sh.wgs;
+}
+
+// ---------------------------------------------------------------------------
+// qba_montecarlo_curve_sampled: the same instances decided at every checkpoint
+// c_0 < c_1 < ... of one pass over their entries.
+// Entry e depends on e and the key alone, so the entries at count c are the
+// first c of any larger count, and the masks are monotone reductions over them:
+// the wave keeps running masks in an accumulator area of its own
+// (mc_acc_begin, qba_proto_rounds.h) behind its mailbox, adds the entries of
+// the segment [c_(j-1), c_j), and at c_j turns a copy into S.tab / S.rep and
+// runs the rounds into row j -- which seed their streams from the key alone,
+// so row j is the row of qba_k_mc_sampled at count c_j.
+// ---------------------------------------------------------------------------
+__host__ __device__ constexpr size_t qba_mc_acc_lds(int G, int w) {
+  return (size_t)((mc_acc_words(G, w) + 3) & ~3) * sizeof(uint32_t);
+}
+template <int NP, int SAMP>
+constexpr int qba_mc_curve_waves() {
+  using C = QCfg<NP>;
+  return qba_mc_shape(qba_mc_tables<NP, SAMP>(), C::G, C::W, 16, qba_mc_acc_lds(C::G, C::W)).waves;
+}
+
+template <int NP, int SAMP, int NW>
+__global__ void __attribute__((amdgpu_flat_work_group_size(64, NW * 64)))
+    qba_k_mc_curve_sampled(const QbaProgramSet *__restrict__ ps, uint64_t seed_base, int64_t n_inst, int n_dis,
+                           int nw_run, int32_t *__restrict__ out, const QbaMcCounts cv) {
+  using C = QCfg<NP>;
+  constexpr int ND = CF<NP>::ND;
+  constexpr size_t WAVE_WORDS = (qba_mc_wave_lds(C::G, C::W) + qba_mc_acc_lds(C::G, C::W)) / sizeof(uint32_t);
+  extern __shared__ __align__(16) uint64_t lds[];
+  const uint64_t *pat, *apat, *thr;
+  const uint32_t *pl;
+  uint32_t *waves = qba_stage<NP, 1, SAMP, NW * 64>(ps, lds, pat, apat, thr, pl);
+  __syncthreads();
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = (int)__lane_id();
+  if (wv >= nw_run) return;
+  uint32_t *mine = waves + (size_t)wv * WAVE_WORDS;
+  ProtoShared &S = *reinterpret_cast<ProtoShared *>(mine);
+  uint32_t *box = mine + PROTO_S_WORDS;
+  uint32_t *acc = mine + qba_mc_wave_lds(C::G, C::W) / sizeof(uint32_t);
+  uint32_t *mcw = acc + C::W * C::G;  // the AND words and the flags, as mc_entry addresses them
+  const int64_t stride = (int64_t)gridDim.x * nw_run;
+  for (int64_t inst = (int64_t)blockIdx.x * nw_run + wv; inst < n_inst; inst += stride) {
+    const uint64_t key = seed_base + (uint64_t)inst;
+    const uint32_t k0 = __builtin_amdgcn_readfirstlane((uint32_t)key);
+    const uint32_t k1 = __builtin_amdgcn_readfirstlane((uint32_t)(key >> 32));
+    mc_acc_begin(acc, C::G, C::W, lane);  // nothing but the segments touches the area
+    uint32_t seen = 0, bad = 0, lo = 0;
+    for (int j = 0; j < cv.n; ++j) {
+      const uint32_t hi = cv.c[j];
+      proto_sync<false>();  // the area is set up; the previous row's stores have read S
+      if constexpr (SAMP == QBA_S_CLOSED) {
+        // pairs [lo / 2, ceil(hi / 2)), lane l the l-th, l + 64-th, ... of them;
+        // a checkpoint at an odd count splits a pair, whose block is then drawn
+        // in both segments and gives each its half
+        const uint32_t pend = (hi + 1u) >> 1;
+        for (uint32_t p = (lo >> 1) + (uint32_t)lane; p < pend; p += 64u) {
+          const QbaU4 x = qba_philox(p, 0u, 0u, 0u, k0, k1);
+#pragma unroll
+          for (uint32_t h = 0; h < 2; ++h) {
+            const uint32_t e = 2u * p + h;
+            if (e < lo || e >= hi) continue;
+            uint32_t d[ND], D[4] = {0u, 0u, 0u, 0u};
+            qba_closed_half<NP>(h ? x.z : x.x, h ? x.w : x.y, (uint64_t)p, h, k0, k1, pl, d);
+#pragma unroll
+            for (int i = 0; i < ND; ++i) D[i] = d[i];
+            mc_entry_at<false>(acc, C::G, mcw, D, C::G, C::W, seen, bad);
+          }
+        }
+      } else {
+        for (uint32_t e = lo + (uint32_t)lane; e < hi; e += 64u) {
+          uint32_t d[ND], D[4] = {0u, 0u, 0u, 0u};
+          qba_entry_d<NP, SAMP>((uint64_t)e, k0, k1, ps, pat, apat, thr, pl, d);
+#pragma unroll
+          for (int i = 0; i < ND; ++i) D[i] = d[i];
+          mc_entry_at<false>(acc, C::G, mcw, D, C::G, C::W, seen, bad);
+        }
+      }
+      mc_flags(mcw, C::G, C::W, seen, bad);
+      proto_sync<false>();
+      uint32_t st;
+      const uint32_t pnz = mc_acc_finish<false>(S, acc, C::G, C::W, lane, st);
+      proto_sync<false>();
+      proto_rounds<false>(S, box, NP, n_dis, key, pnz, st, lane,
+                          out + ((int64_t)j * n_inst + inst) * (int64_t)(4 + 5 * C::G));
+      lo = hi;
+    }
+    proto_sync<false>();  // the last finish has read the area
+  }
+}
+
+template <int NP, int SAMP>
+static int qba_launch_mc_curve_s(qba_ctx *ctx, const QbaMcCurve &M, size_t tables) {
+  using C = QCfg<NP>;
+  constexpr int NW = qba_mc_curve_waves<NP, SAMP>();
+  static_assert(NW >= 1, "no room for a wave beside the tables");
+  const QbaMcShape sh = qba_mc_shape(tables, C::G, C::W, NW, qba_mc_acc_lds(C::G, C::W));
+  if (sh.waves < 1)
+    return qba_fail(QBA_EUNSUPPORTED, "qba_montecarlo_curve_sampled: the program's tables leave no LDS for a wave");
+  const void *kern = (const void *)qba_k_mc_curve_sampled<NP, SAMP, NW>;
+  if (int rc = lds_allow(kern, sh.lds)) return rc;
+  const int64_t need = (M.n_inst + sh.waves - 1) / sh.waves, cap = (int64_t)ctx->num_cus * sh.wgs;
+  const int grid = (int)(need < cap ? need : cap);
+  const int nw_run = sh.waves;
+  const void *args[] = {&M.ps, &M.seed_base, &M.n_inst, &M.n_dis, &nw_run, &M.out, &M.counts};
+  QBA_HIP(hipLaunchKernel(kern, dim3(grid), dim3(NW * 64), const_cast<void **>(args), sh.lds, M.stream));
+  QBA_HIP(hipGetLastError());
+  return QBA_OK;
+}
+
+template <int NP>
+int qba_launch_mc_curve(qba_ctx *ctx, const QbaMcCurve &M) {
+  const QbaProgramSet *hs = reinterpret_cast<const QbaProgramSet *>(ctx->prog_host[NP]);
+  const int samp = sampler_of<NP>(hs);
+  if (int rc = check_closed<NP>(hs)) return rc;
+  const size_t tables = table_lds<NP>(hs, samp);
+  if (samp == QBA_S_CLOSED) {
+    if constexpr (NP <= QBA_CLOSED_MAX_N) return qba_launch_mc_curve_s<NP, QBA_S_CLOSED>(ctx, M, tables);
+    return qba_fail(QBA_EUNSUPPORTED, "closed form beyond n = 11");
+  }
+  if (samp == QBA_S_FAST) return qba_launch_mc_curve_s<NP, QBA_S_FAST>(ctx, M, tables);
+  return qba_launch_mc_curve_s<NP, QBA_S_GENERAL>(ctx, M, tables);
+}
+
+template <int NP>
+void qba_mc_curve_shape_n(int *waves, int64_t *lds, int *wgs) {
+  using C = QCfg<NP>;
+  constexpr int SAMP = NP <= QBA_CLOSED_MAX_N ? QBA_S_CLOSED : QBA_S_FAST;
+  constexpr QbaMcShape sh = qba_mc_shape(qba_mc_tables<NP, SAMP>(), C::G, C::W, 16, qba_mc_acc_lds(C::G, C::W));
   *waves = sh.waves;
   *lds = (int64_t)sh.lds;
   *wgs = sh.wgs;

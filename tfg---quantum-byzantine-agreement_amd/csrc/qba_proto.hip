@@ -4,7 +4,8 @@
 //                          qba_sample_check_batched, exactly as
 //                          countmode.CountParty does under protocol.run_local
 //                          (barrier-epoch delivery, comm.py);
-//   qba_montecarlo_lists   from injected byte rows, with no tables in between.
+//   qba_montecarlo_lists   from injected byte rows, with no tables in between;
+//   qba_montecarlo_curve_lists  the same at several counts in one pass.
 // The rounds themselves are qba_proto_rounds.h (shared with the sampling
 // kernel qba_k_mc_sampled); this file holds what feeds them.  DESIGN.md
 // section 13.
@@ -107,6 +108,49 @@ __global__ __launch_bounds__(QBA_PROTO_BLOCK) void qba_k_mc_lists(int n, int n_d
                      out + inst * (int64_t)(4 + 5 * G));
 }
 
+// qba_k_mc_lists at the checkpoints cv.c[0] < cv.c[1] < ...: the running masks
+// of the entries so far live in an accumulator area behind the mailbox
+// (mc_acc_begin, qba_proto_rounds.h), which the rounds leave alone; row j is
+// the row of qba_k_mc_lists at count cv.c[j].  A value >= w at a Q-correlated
+// position sets the flag from its segment's checkpoint on.
+__global__ __launch_bounds__(QBA_PROTO_BLOCK) void qba_k_mc_curve_lists(int n, int n_dis, uint64_t seed_base,
+                                                                        int64_t inst0, int64_t n_inst,
+                                                                        const uint8_t *__restrict__ lists,
+                                                                        uint64_t ld, uint64_t inst_stride,
+                                                                        int32_t *__restrict__ out,
+                                                                        const QbaMcCounts cv) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];  // ProtoShared | box [2][G][box_ld] | acc
+  ProtoShared &S = *reinterpret_cast<ProtoShared *>(lds);
+  uint32_t *box = lds + PROTO_S_WORDS;
+  const int lane = threadIdx.x;
+  const int G = n + 1, nq = 32 - __clz(n), w = 1 << nq;
+  uint32_t *acc = box + ((proto_box_words(G, w) + 3) & ~3);
+  uint32_t *mcw = acc + w * G;
+  const int64_t inst = inst0 + blockIdx.x;
+  const uint8_t *L = lists + (uint64_t)inst * inst_stride;
+  mc_acc_begin(acc, G, w, lane);
+  uint32_t seen = 0, bad = 0, lo = 0;
+  for (int j = 0; j < cv.n; ++j) {
+    const uint32_t hi = cv.c[j];
+    proto_sync<true>();
+    for (uint32_t k = lo + (uint32_t)lane; k < hi; k += 64u) {
+      uint32_t D[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int g = 0; g < QBA_PROTO_MAXG; ++g)
+        if (g < G) D[g / 4] |= (uint32_t)L[(uint64_t)g * ld + k] << (8 * (g % 4));
+      mc_entry_at<true>(acc, G, mcw, D, G, w, seen, bad);
+    }
+    mc_flags(mcw, G, w, seen, bad);
+    proto_sync<true>();
+    uint32_t st;
+    const uint32_t pnz = mc_acc_finish<true>(S, acc, G, w, lane, st);
+    proto_sync<true>();
+    proto_rounds<true>(S, box, n, n_dis, seed_base + (uint64_t)inst, pnz, st, lane,
+                       out + ((int64_t)j * n_inst + inst) * (int64_t)(4 + 5 * G));
+    lo = hi;
+  }
+}
+
 }  // namespace
 
 extern "C" int qba_protocol_batched(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
@@ -162,6 +206,49 @@ extern "C" int qba_montecarlo_lists(qba_ctx *ctx, int n, int n_dis, uint64_t see
     const int64_t blocks = n_inst - first < QBA_PROTO_LAUNCH ? n_inst - first : QBA_PROTO_LAUNCH;
     hipLaunchKernelGGL(qba_k_mc_lists, dim3((unsigned)blocks), dim3(QBA_PROTO_BLOCK), lds, (hipStream_t)stream, n,
                        n_dis, seed_base, first, (uint32_t)count, lists, ld, inst_stride, out);
+    QBA_HIP(hipGetLastError());
+  }
+  return QBA_OK;
+}
+
+int qba_mc_curve_check(const char *who, qba_ctx *ctx, int n, int n_dis, int64_t n_inst, const uint32_t *counts,
+                       int n_counts, const void *out, QbaMcCounts *cv) {
+  const std::string f(who);
+  if (n < 1 || n > QBA_MAX_PARTIES) return qba_fail(QBA_EINVAL, f + ": n_parties must be in [1, 15]");
+  if (n_dis < 0 || n_dis > n) return qba_fail(QBA_EINVAL, f + ": n_dishonest must be in [0, n_parties]");
+  if (!counts) return qba_fail(QBA_EINVAL, f + ": counts is NULL");
+  if (n_counts < 1 || n_counts > QBA_MC_CURVE_MAX) return qba_fail(QBA_EINVAL, f + ": n_counts must be in [1, 32]");
+  for (int j = 1; j < n_counts; ++j)
+    if (counts[j] <= counts[j - 1]) return qba_fail(QBA_EINVAL, f + ": counts must be strictly increasing");
+  if (counts[n_counts - 1] >= (1u << 31)) return qba_fail(QBA_EINVAL, f + ": counts must be < 2^31");
+  if (!ctx) return qba_fail(QBA_EINVAL, f + ": ctx is NULL");
+  if (n_inst < 0) return qba_fail(QBA_EINVAL, f + ": n_instances < 0");
+  if (n_inst > 0 && !out) return qba_fail(QBA_EINVAL, f + ": out is NULL");
+  *cv = QbaMcCounts{};
+  for (int j = 0; j < n_counts; ++j) cv->c[j] = counts[j];
+  cv->n = n_counts;
+  return QBA_OK;
+}
+
+extern "C" int qba_montecarlo_curve_lists(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
+                                          const uint32_t *counts, int n_counts, const uint8_t *lists, uint64_t ld,
+                                          uint64_t inst_stride, int32_t *out, qba_stream stream) {
+  QbaMcCounts cv;
+  int rc = qba_mc_curve_check("qba_montecarlo_curve_lists", ctx, n, n_dis, n_inst, counts, n_counts, out, &cv);
+  if (rc) return rc;
+  const uint64_t cmax = cv.c[cv.n - 1];
+  if (cmax && n_inst && (!lists || ld < cmax || (n_inst > 1 && inst_stride < (uint64_t)(n + 1) * ld)))
+    return qba_fail(QBA_EINVAL,
+                    "qba_montecarlo_curve_lists: need lists, ld >= the last count and inst_stride >= (n+1)*ld");
+  if (n_inst == 0) return QBA_OK;
+  if ((rc = qba_set_device(ctx))) return rc;
+  const int G = n + 1, w = 1 << qba_nq(n);
+  const size_t lds = (size_t)(PROTO_S_WORDS + ((proto_box_words(G, w) + 3) & ~3) + mc_acc_words(G, w)) *
+                     sizeof(uint32_t);  // <= 37024 B
+  for (int64_t first = 0; first < n_inst; first += QBA_PROTO_LAUNCH) {
+    const int64_t blocks = n_inst - first < QBA_PROTO_LAUNCH ? n_inst - first : QBA_PROTO_LAUNCH;
+    hipLaunchKernelGGL(qba_k_mc_curve_lists, dim3((unsigned)blocks), dim3(QBA_PROTO_BLOCK), lds, (hipStream_t)stream,
+                       n, n_dis, seed_base, first, n_inst, lists, ld, inst_stride, out, cv);
     QBA_HIP(hipGetLastError());
   }
   return QBA_OK;

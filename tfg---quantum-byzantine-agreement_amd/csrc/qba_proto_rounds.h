@@ -3,6 +3,7 @@
 //   qba_k_protocol (qba_proto.hip)     distils the int64 count tables
 //   qba_k_mc_lists (qba_proto.hip)     distils injected byte rows
 //   qba_k_mc_sampled (qba_mc_kern.h)   distils the entries it samples itself
+//   qba_k_mc_curve_sampled / _lists    the same two at several counts in one pass
 // Each brings the distilled state -- pnz (bit u: P_u is not empty) and, in
 // ProtoShared, per (u, g) the mask of x with H[u][g][x] != 0, the mask of h
 // with C[u][g][h] == 0 and rep(u, g) = min h with C[u][g][h] == |P_u| -- and
@@ -318,6 +319,41 @@ __device__ __forceinline__ void mc_begin(ProtoShared &S, uint32_t *mcw, int G, i
 // One entry, group g = byte g % 4 of D[g / 4] (the layout of qba_entry_d).
 // RANGE: the values are untrusted; an entry with one >= w is flagged and left
 // out (its u could index past the masks).  seen: this lane's distinct-entry bits.
+// mc_entry_at (the curve kernels): the OR words are tab[u * tld + g], an
+// accumulator area with rows G apart.  mc_entry below is the same body on
+// S.tab; it is kept as its own text, because routing it through mc_entry_at
+// changed the code the compiler emits for qba_k_mc_sampled at n >= 7, and the
+// existing kernels stay byte for byte what they were.
+template <bool RANGE>
+__device__ __forceinline__ void mc_entry_at(uint32_t *tab, int tld, uint32_t *mcw, const uint32_t (&D)[4], int G,
+                                            int w, uint32_t &seen, uint32_t &bad) {
+  const uint32_t l0 = D[0] & 0xffu, u = (D[0] >> 8) & 0xffu;
+  if (l0 == u) return;  // not Q-correlated (tfg.py:327)
+  uint32_t U = 0, hi = 0;
+  for (int g = 0; g < G; ++g) {
+    const uint32_t v = qba_byte_at(D, g);
+    hi |= v;
+    U |= 1u << (v & 15u);
+  }
+  if (RANGE && hi >= (uint32_t)w) {
+    bad = 1u;
+    return;
+  }
+  uint32_t *t = &tab[u * tld];
+  if (__popc(U) == G) {  // pairwise distinct: E(g) = {g}
+    for (int g = 0; g < G; ++g) atomicOr(&t[g], (1u << qba_byte_at(D, g)) | (0x10000u << g));
+    seen |= 1u << u;
+    return;
+  }
+  for (int g = 0; g < G; ++g) {
+    const uint32_t v = qba_byte_at(D, g);
+    uint32_t eq = 0;
+    for (int h = 0; h < G; ++h) eq |= (uint32_t)(qba_byte_at(D, h) == v) << h;
+    atomicOr(&t[g], (1u << v) | (eq << 16));
+    atomicAnd(&mcw[u * G + g], eq);
+  }
+}
+
 template <bool RANGE>
 __device__ __forceinline__ void mc_entry(ProtoShared &S, uint32_t *mcw, const uint32_t (&D)[4], int G, int w,
                                          uint32_t &seen, uint32_t &bad) {
@@ -370,6 +406,46 @@ __device__ __forceinline__ uint32_t mc_finish(ProtoShared &S, uint32_t *mcw, int
     const uint32_t t = S.tab[at];
     S.tab[at] = (t & 0xFFFFu) | ((~(t >> 16) & ((1u << G) - 1u)) << 16);
     S.rep[at] = (uint8_t)(__ffs((int)a) - 1);  // a keeps bit g at least: g is in every E(g)
+  }
+  proto_sync<WG>();
+  uint32_t pnz = 0;
+  for (int u = 0; u < w; ++u) pnz |= (uint32_t)((S.tab[u * QBA_PROTO_MAXG] & 0xFFFFu) != 0u) << u;
+  return pnz;
+}
+
+// ---------------------------------------------------------------------------
+// The curve kernels decide one instance at several counts c_0 < c_1 < ...: the
+// masks at count c are the reductions over the entries [0, c), so they keep
+// RUNNING masks over the segments [c_(j-1), c_j) and run the rounds at every
+// c_j.  mc_finish complements S.tab in place and the rounds write the mailbox,
+// so the running masks live in an accumulator area of the wave's own, outside
+// ProtoShared and the mailbox, that only the segments write:
+//   acc[u * G + g]          the two ORs, as S.tab[u][g] holds them while an
+//                           instance is distilled (mc_entry_at, rows G apart)
+//   acc[w * G + ...]        the AND words and the two flag words, laid out as
+//                           mc_entry / mc_flags lay them out in the mailbox
+// mc_acc_finish is mc_finish reading the area and writing S.tab / S.rep: the
+// area stays as it was, and the next segment goes on from it.
+// ---------------------------------------------------------------------------
+__host__ __device__ constexpr int mc_acc_words(int G, int w) { return 2 * w * G + 2; }
+
+__device__ __forceinline__ void mc_acc_begin(uint32_t *acc, int G, int w, int lane) {
+  for (int i = lane; i < 2 * w * G + 2; i += 64) acc[i] = i >= w * G && i < 2 * w * G ? 0xFFFFFFFFu : 0u;
+}
+
+template <bool WG>
+__device__ __forceinline__ uint32_t mc_acc_finish(ProtoShared &S, const uint32_t *acc, int G, int w, int lane,
+                                                  uint32_t &st) {
+  const uint32_t *mcw = acc + w * G;
+  const uint32_t seen = mcw[w * G];
+  st = mcw[w * G + 1] ? QBA_PROTO_ST_RANGE : 0u;
+  for (int e = lane; e < w * G; e += 64) {
+    const int u = e / G, g = e - u * G, at = u * QBA_PROTO_MAXG + g;
+    uint32_t a = mcw[e];
+    if ((seen >> u) & 1u) a &= 1u << g;
+    const uint32_t t = acc[e];
+    S.tab[at] = (t & 0xFFFFu) | ((~(t >> 16) & ((1u << G) - 1u)) << 16);
+    S.rep[at] = (uint8_t)(__ffs((int)a) - 1);
   }
   proto_sync<WG>();
   uint32_t pnz = 0;

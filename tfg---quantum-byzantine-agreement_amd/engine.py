@@ -333,6 +333,86 @@ class Engine:
              _ptr(lists), ld, stride, _ptr(out), self.stream())
         return out
 
+    # -- a whole sizeL curve in one pass (qba_montecarlo_curve_*) ------------------
+    CURVE_MAX = 32  # QBA_MC_CURVE_MAX
+
+    @classmethod
+    def _check_curve(cls, n: int, n_dishonest: int, n_inst: int, counts) -> list:
+        """The checkpoints as a list of ints; validation as _check_mc."""
+        try:
+            cs = [int(c) for c in counts]
+        except TypeError:
+            raise QbaError("counts must be a sequence of integers") from None
+        if not 0 <= n_dishonest <= n:
+            raise QbaError(f"n_dishonest={n_dishonest} outside [0, {n}]")
+        if not 1 <= len(cs) <= cls.CURVE_MAX:
+            raise QbaError(f"between 1 and {cls.CURVE_MAX} checkpoints, not {len(cs)}")
+        if any(b <= a for a, b in zip(cs, cs[1:])) or cs[0] < 0 or cs[-1] >= 1 << 31:
+            raise QbaError("counts must be strictly increasing, with 0 <= counts[0] and counts[-1] < 2^31")
+        if n_inst < 0:
+            raise QbaError("n_inst >= 0")
+        return cs
+
+    def _curve_out(self, n: int, k: int, n_inst: int, out: Optional[torch.Tensor]) -> torch.Tensor:
+        shape = (k, n_inst, 4 + 5 * (n + 1))
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=self.device)
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != shape or \
+                not out.is_contiguous() or out.device != self.device:
+            raise QbaError(f"out must be a contiguous int32 {list(shape)} device tensor")
+        return out
+
+    def montecarlo_curve_sampled(self, n: int, n_dishonest: int, seed_base: int, n_inst: int, counts,
+                                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The n_inst instances of montecarlo_sampled decided at every count of
+        the strictly increasing ``counts`` (at most 32) in one pass over their
+        entries (qba_montecarlo_curve_sampled): int32 [len(counts), n_inst,
+        4 + 5*(n+1)], slice j word for word montecarlo_sampled(count=counts[j])."""
+        self._check_n(n)
+        cs = self._check_curve(n, n_dishonest, n_inst, counts)
+        self.prepare(n)
+        out = self._curve_out(n, len(cs), n_inst, out)
+        arr = (C.c_uint32 * len(cs))(*cs)
+        call("qba_montecarlo_curve_sampled", self.ctx, n, n_dishonest, int(seed_base) & ((1 << 64) - 1), n_inst, arr,
+             len(cs), _ptr(out), self.stream())
+        return out
+
+    def montecarlo_curve_lists(self, n: int, n_dishonest: int, seed_base: int, lists, counts,
+                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The same from injected lists (qba_montecarlo_curve_lists), uint8
+        [n_inst, n+1, >= counts[-1]] as montecarlo_lists takes them: slice j is
+        montecarlo_lists(count=counts[j]).  A value >= w at Q-correlated
+        position k gives status 4 in exactly the slices with counts[j] > k."""
+        self._check_n(n)
+        if isinstance(lists, np.ndarray):
+            lists = torch.from_numpy(np.array(lists, dtype=np.uint8, order="C")).to(self.device)  # a writable copy
+        if not isinstance(lists, torch.Tensor) or lists.dtype != torch.uint8 or lists.dim() != 3 or \
+                lists.shape[1] != n + 1 or lists.device != self.device or (lists.numel() and lists.stride(2) != 1):
+            raise QbaError("lists must be a uint8 [n_inst, n+1, >= counts[-1]] device tensor with unit column stride")
+        n_inst = lists.shape[0]
+        cs = self._check_curve(n, n_dishonest, n_inst, counts)
+        cmax = cs[-1]
+        if lists.shape[2] < cmax:
+            raise QbaError("lists must be a uint8 [n_inst, n+1, >= counts[-1]] device tensor with unit column stride")
+        ld, stride = (lists.stride(1), lists.stride(0)) if lists.numel() else (cmax, (n + 1) * cmax)
+        if cmax and n_inst and (ld < cmax or (n_inst > 1 and stride < (n + 1) * ld)):
+            raise QbaError("lists rows overlap: need stride(1) >= counts[-1] and stride(0) >= (n+1)*stride(1)")
+        out = self._curve_out(n, len(cs), n_inst, out)
+        arr = (C.c_uint32 * len(cs))(*cs)
+        call("qba_montecarlo_curve_lists", self.ctx, n, n_dishonest, int(seed_base) & ((1 << 64) - 1), n_inst, arr,
+             len(cs), _ptr(lists), ld, stride, _ptr(out), self.stream())
+        return out
+
+    @classmethod
+    def montecarlo_curve_shape(cls, n: int) -> Tuple[int, int, int]:
+        """(wavefronts per workgroup, dynamic LDS bytes of a workgroup,
+        workgroups per CU) of montecarlo_curve_sampled's kernel for the standard
+        programs (qba_montecarlo_curve_shape); needs no device."""
+        cls._check_n(n)
+        waves, lds, wgs = C.c_int(), C.c_int64(), C.c_int()
+        call("qba_montecarlo_curve_shape", n, C.byref(waves), C.byref(lds), C.byref(wgs))
+        return waves.value, lds.value, wgs.value
+
     # -- (A5-A8) count mode -------------------------------------------------------
     def check_counts(self, lists: torch.Tensor, n: int, count: int,
                      counts: Optional[Counts] = None, accumulate: bool = False) -> Counts:

@@ -26,6 +26,12 @@ The fused path (``run(path="fused")``, ``Engine.montecarlo_sampled`` /
 fact that the rounds consult only bitwise reductions over an instance's
 Q-correlated entries, restated on the host by :func:`masks_from_lists` and
 :func:`masks_from_tables`.
+
+A whole sizeL curve (:func:`curve`, ``Engine.montecarlo_curve_sampled`` /
+``montecarlo_curve_lists``) decides the same instances at several sizeL in one
+pass: the lists at sizeL = c are the first c columns of the lists at any larger
+sizeL, and those reductions are monotone.  :func:`curve_host` is its
+specification.
 """
 from __future__ import annotations
 
@@ -284,3 +290,33 @@ def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, pack
         outs.append(engine.protocol_batched(n, n_dishonest, key, counts))
     rows = torch.cat(outs).cpu().numpy() if outs else np.zeros((0, out_words(n)), np.int32)
     return summarize(n, rows)
+
+
+def curve_host(n: int, counts, n_dishonest: int, n_inst: int, seed_base: int, engine, lists=None) -> np.ndarray:
+    """The specification of the curve calls: the stack of :func:`run_host` at
+    each count of ``counts``, int32 [len(counts), n_inst, out_words(n)].
+    Injected ``lists`` [n_inst, n+1, >= max(counts)] are truncated to
+    ``[:, :, :c]`` for the count c."""
+    counts = [int(c) for c in counts]
+    li = None if lists is None else np.asarray(lists)
+    rows = [run_host(n, c, n_dishonest, n_inst, seed_base, engine, lists=None if li is None else li[:, :, :c])
+            for c in counts]
+    return np.stack(rows) if rows else np.zeros((0, n_inst, out_words(n)), np.int32)
+
+
+def curve(n: int, counts, n_dishonest: int, runs: int, seed: int, engine, batch: int = 4096) -> dict:
+    """The failure curve over sizeL: ``runs`` instances, ``batch`` at a time as
+    :func:`run` keys them, each decided at every sizeL of the strictly
+    increasing ``counts`` by one montecarlo_curve_sampled call per batch.
+    Returns ``{sizeL: summarize(...)}`` in checkpoint order; the summary at
+    sizeL = c is that of ``run(n, c, ..., path="fused")``."""
+    import torch
+    if runs < 0 or batch < 1:
+        raise ValueError("runs >= 0 and batch >= 1")
+    counts = [int(c) for c in counts]
+    outs = []
+    for off in range(0, runs, batch):
+        b = min(batch, runs - off)
+        outs.append(engine.montecarlo_curve_sampled(n, n_dishonest, (int(seed) + off) & MASK64, b, counts))
+    rows = torch.cat(outs, dim=1).cpu().numpy() if outs else np.zeros((len(counts), 0, out_words(n)), np.int32)
+    return {c: summarize(n, rows[j]) for j, c in enumerate(counts)}

@@ -41,6 +41,13 @@ from . import countmode, protocol
 RCCL_ID_TAG = 29_999
 
 
+CURVE_MAX = 32  # checkpoints of one --curve run (QBA_MC_CURVE_MAX)
+
+
+def _sizes(text: str):
+    return [int(float(x)) for x in text.split(",") if x.strip()]
+
+
 def _args(argv):
     ap = argparse.ArgumentParser(prog="tfg", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -58,12 +65,25 @@ def _args(argv):
     ap.add_argument("--fused", action="store_true",
                     help="with --runs: sample, distil and decide each batch in one kernel, with no list buffer and "
                          "no count tables (montecarlo.run path='fused'); the same instances and summary")
+    ap.add_argument("--curve", type=_sizes, default=None, metavar="C0,C1,...",
+                    help="with --runs: decide every instance at each of these sizeL and at the positional sizeL in "
+                         "one pass per batch (montecarlo.curve; at most 32 in all); one summary line per sizeL, "
+                         "increasing; implies --fused")
     ap.add_argument("--quiet", action="store_true", help="print only the outcome")
     ap.add_argument("--timing", action="store_true", help="print the wall time of the run")
     ap.add_argument("--wire", action="store_true",
                     help="in-process exact mode: send the lists in the reference's int64-per-bit wire layout "
                          "(tfg.py:142-161) instead of handing each rank its device row")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.curve is not None:
+        if a.runs is None:
+            ap.error("--curve needs --runs")
+        a.curve = sorted(set(a.curve) | {int(a.sizeL)})
+        if len(a.curve) > CURVE_MAX:
+            ap.error(f"--curve: at most {CURVE_MAX} checkpoints (the positional sizeL included), not {len(a.curve)}")
+        if a.curve[0] < 0 or a.curve[-1] >= 1 << 31:
+            ap.error("--curve: every sizeL must be in [0, 2^31)")
+    return a
 
 
 def _outcome(res, verbose):
@@ -177,14 +197,19 @@ def _torchrun(a, size_l, verbose, log) -> int:
 
 def _montecarlo(a, eng, size_l) -> int:
     """--runs R: R independent count-mode instances decided on the device
-    (montecarlo.run); one summary line."""
+    (montecarlo.run); one summary line, or with --curve one per sizeL
+    (montecarlo.curve)."""
     from . import montecarlo
     seed = secrets.randbits(62) if a.seed is None else a.seed
     t0 = time.perf_counter()
-    s = montecarlo.run(a.parties, size_l, a.nDishonest, a.runs, seed, eng, batch=a.batch,
-                       path="fused" if a.fused else "tables")
-    print(f"Runs: {s['runs']} Successes: {s['successes']} Rate: {s['rate']:.6f} "
-          f"(n={a.parties}, sizeL={size_l}, dishonest={a.nDishonest}, empty-V_i runs={s['empty_vi_runs']})")
+    if a.curve is not None:
+        points = montecarlo.curve(a.parties, a.curve, a.nDishonest, a.runs, seed, eng, batch=a.batch)
+    else:
+        points = {size_l: montecarlo.run(a.parties, size_l, a.nDishonest, a.runs, seed, eng, batch=a.batch,
+                                         path="fused" if a.fused else "tables")}
+    for c, s in points.items():
+        print(f"Runs: {s['runs']} Successes: {s['successes']} Rate: {s['rate']:.6f} "
+              f"(n={a.parties}, sizeL={c}, dishonest={a.nDishonest}, empty-V_i runs={s['empty_vi_runs']})")
     if a.timing:
         print(f"wall {time.perf_counter() - t0:.3f} s ({a.runs} instances on the device)")
     return 0

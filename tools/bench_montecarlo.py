@@ -14,7 +14,12 @@ instances x n = 7 x sizeL = 1e5, 2 dishonest, on one GPU.
       --sizeL may be given several times (the fused path is meant for small
       ones); --host-instances 0 skips (c).
 
-(a), (b) and (d) are device-event times of single calls on warm code: median, min
+  --curve c0,c1,...  (repeatable) another mode: one montecarlo_curve_sampled
+      call over the checkpoints against the K montecarlo_sampled calls at the
+      same counts, the K timed as one interval; the rows of the two are compared
+      at the timed shape.  One JSON line per --curve; nothing else is measured.
+
+(a), (b), (d) and the --curve pair are device-event times of single calls on warm code: median, min
 and max over --repeats launches after --warmup launches.  (c) is host wall
 time around runs that end in device synchronisation (each reads its tables
 back).  Prints one JSON line; --out also writes it to a file.  No GPU: fails.
@@ -59,16 +64,51 @@ def main(argv=None) -> int:
     ap.add_argument("--repeats", type=int, default=50)
     ap.add_argument("--seed", type=int, default=0x5EED)
     ap.add_argument("--out", type=Path, default=None)
+    ap.add_argument("--curve", action="append", default=None, metavar="C0,C1,...",
+                    help="time one curve call against the separate calls at these counts; repeatable")
     a = ap.parse_args(argv)
 
     eng = importlib.import_module(f"{PKG}.engine").Engine(0)
-    lines = [json.dumps(_measure(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
+    if a.curve:
+        lines = [json.dumps(_measure_curve(a, eng, sorted({int(c) for c in text.split(",")}))) for text in a.curve]
+    else:
+        lines = [json.dumps(_measure(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
     print("\n".join(lines))
     if a.out is not None:
         a.out.parent.mkdir(parents=True, exist_ok=True)
         a.out.write_text("\n".join(lines) + "\n")
     eng.close()
     return 0
+
+
+def _measure_curve(a, eng, counts) -> dict:
+    import torch
+    n, nd, inst = a.parties, a.dishonest, a.instances
+    curve = eng.montecarlo_curve_sampled(n, nd, a.seed, inst, counts)
+    single = torch.empty_like(curve)
+
+    def separate():
+        for j, c in enumerate(counts):
+            eng.montecarlo_sampled(n, nd, a.seed, inst, c, single[j])
+
+    separate()
+    torch.cuda.synchronize()
+    waves, lds, wgs = eng.montecarlo_curve_shape(n)
+    res = {"config": {"n": n, "counts": counts, "dishonest": nd, "instances": inst, "seed": a.seed,
+                      "device": torch.cuda.get_device_name(0), "entries_curve": counts[-1],
+                      "entries_separate": sum(counts),
+                      "curve_shape": {"waves": waves, "lds_bytes": lds, "wgs_per_cu": wgs}},
+           "rows_equal_separate_calls": bool(torch.equal(curve, single))}
+    res["separate_montecarlo_sampled"] = _events(separate, a.warmup, a.repeats)
+    res["curve_montecarlo_curve_sampled"] = _events(
+        lambda: eng.montecarlo_curve_sampled(n, nd, a.seed, inst, counts, curve), a.warmup, a.repeats)
+    res["rows_equal_separate_calls"] = res["rows_equal_separate_calls"] and bool(torch.equal(curve, single))
+    s, c = res["separate_montecarlo_sampled"], res["curve_montecarlo_curve_sampled"]
+    res["separate_over_curve_at_median"] = s["median_ms"] / c["median_ms"]
+    # faster only where the min-max ranges do not overlap
+    res["curve_faster"] = c["max_ms"] < s["min_ms"]
+    res["separate_faster"] = s["max_ms"] < c["min_ms"]
+    return res
 
 
 def _measure(a, eng, size_l) -> dict:
