@@ -323,6 +323,20 @@ QBA_API int qba_montecarlo_curve_lists(qba_ctx *ctx, int n_parties, int n_dishon
  * each wavefront also holds its running masks, 2*w*(n+1) + 2 words (DESIGN.md
  * section 13.2), so some n run fewer wavefronts per workgroup. */
 QBA_API int qba_montecarlo_curve_shape(int n_parties, int *waves, int64_t *lds_bytes, int *wgs_per_cu);
+/* The launch shape of the program compiled for n_parties in ctx right now
+ * (qba_resource_compile; QBA_ESTATE without both kinds), as the launcher of
+ * qba_montecarlo_sampled (curve == 0) or qba_montecarlo_curve_sampled
+ * (curve != 0) would choose it: *sampler 0 general alias tables, 1 canonical
+ * tables, 2 closed form; *waves_compiled the wavefronts per workgroup that
+ * sampler's kernel is built and launched with; *waves_run those of them that
+ * take instances (fewer when the program's tables are not the size the kernel
+ * was built for and another split of the CU's LDS keeps more wavefronts
+ * resident); *lds_bytes and *wgs_per_cu as qba_montecarlo_shape.  For the
+ * standard programs waves_run == waves_compiled and the three values are those
+ * of qba_montecarlo_shape / qba_montecarlo_curve_shape.  Host only: launches
+ * nothing, touches no device. */
+QBA_API int qba_montecarlo_program_shape(qba_ctx *ctx, int n_parties, int curve, int *sampler, int *waves_compiled,
+                                         int *waves_run, int64_t *lds_bytes, int *wgs_per_cu);
 
 /* ---- (A5-A8) checks, exact-order mode (bit-exact protocol parity) --------------- */
 /* isQCorrList = {k : Li[k] != Lc[k]} (tfg.py:327) as ascending indices.

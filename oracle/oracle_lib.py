@@ -5,6 +5,7 @@ bench.py's cpu_baseline leg; never by the product package.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from pathlib import Path
 
@@ -140,3 +141,15 @@ def batched_counts(n: int, seed_base: int, n_inst: int, count: int, prog_notq: d
 
 def threads() -> int:
     return int(lib().oracle_threads())
+
+
+@contextlib.contextmanager
+def single_thread():
+    """Run the twin's calls inside on one thread: for many calls on tiny inputs
+    a thread team per call costs more than the work.  Restores the team size."""
+    team = threads()
+    lib().omp_set_num_threads(1)  # resolved through the twin's own OpenMP runtime
+    try:
+        yield
+    finally:
+        lib().omp_set_num_threads(team)

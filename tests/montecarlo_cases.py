@@ -57,6 +57,19 @@ def hostile_lists(case):
     return li
 
 
+def tables_rows(engine, n, nd, base, inst, sizeL, keep_lists=False):
+    """The tables path's rows on the GPU: protocol_batched on the tables of
+    sample_check_batched.  For sizeL = 0 the batched sampler writes nothing,
+    and the rows are defined on all-zero tables."""
+    lists, counts = engine.sample_check_batched(n, base, inst, sizeL)
+    if sizeL == 0:
+        for t in (counts.H, counts.C, counts.P):
+            t.zero_()
+    rows = engine.protocol_batched(n, nd, base, counts).cpu().numpy()
+    rows.setflags(write=False)
+    return (rows, lists) if keep_lists else rows
+
+
 def cpu_lists(n, sizeL, seed_base, n_inst):
     """Injected lists for a host-only evaluation of a set the C twin cannot
     sample (n > 11); None otherwise."""

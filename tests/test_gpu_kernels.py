@@ -9,6 +9,7 @@ import oracle_lib
 import statevector as sv_oracle
 import tfg_oracle as orc
 from conftest import GOLDEN, sub
+from montecarlo_programs import general_pair
 
 pytestmark = pytest.mark.gpu
 
@@ -714,19 +715,6 @@ MATRIX_COUNT, MATRIX_FIRST = 8197, 7  # 1,024 wide units, one whole remaining qu
 MATRIX_SAMPLERS = ["closed3", "closed11", "closed11_pair_bins", "tables12", "general3"]
 
 
-def _general_pair(n):
-    """The circuit pair of test_general_program_path (general alias-table sampler)."""
-    resource = sub("resource")
-    nq = resource.n_qubits(n)
-    notq = resource.Gate((n + 1) * nq)
-    for qb in range(nq, 3 * nq):
-        notq.add_operation("H", targets=qb)
-    for j in range(nq):
-        notq.add_operation("X", targets=j, controls=nq + j)
-        notq.add_operation("X", targets=3 * nq + j, controls=2 * nq + j)
-    return notq, resource.qCorrelated(n, nq, perm=[1, 2, 3])
-
-
 @pytest.fixture(scope="module")
 def matrix(engine):
     """sampler -> (engine, n, oracle rows, oracle (H, C, P)), computed once.
@@ -737,7 +725,7 @@ def matrix(engine):
     for name, eng, n, flags in [("closed3", engine, 3, (True, True)), ("closed11", engine, 11, (True, True)),
                                 ("closed11_pair_bins", forced, 11, (True, True)),
                                 ("tables12", engine, 12, (False, True)), ("general3", forced, 3, (False, False))]:
-        info = eng.compile(n, *_general_pair(n)) if name == "general3" else eng.prepare(n)
+        info = eng.compile(n, *general_pair(n)) if name == "general3" else eng.prepare(n)
         assert (info["closed"], info["canonical"]) == flags, name
         ref = oracle_lib.sample(n, 0xD15 + n, MATRIX_FIRST, MATRIX_COUNT, info["notq"], info["q"], info["closed"])
         H, C, P, bad = oracle_lib.counts(ref, n)

@@ -12,7 +12,7 @@ import pytest
 
 from conftest import GOLDEN, ROOT, sub
 from montecarlo_cases import (CASES, HOSTILE, HOSTILE_IDS, INJECT_BASE, INJECT_KEYS, SWEEP, SWEEP_IDS,
-                              hostile_lists)
+                              hostile_lists, tables_rows)
 from oracle_engine import OracleEngine
 
 pytestmark = pytest.mark.gpu
@@ -39,18 +39,6 @@ def _eq(got, want, what=""):
         i, j = np.argwhere(got != want)[0]
         raise AssertionError(f"{what} instance {i}, word {j}: {got[i, j]} != {want[i, j]}\n"
                              f"got  {got[i].tolist()}\nwant {want[i].tolist()}")
-
-
-def tables_rows(engine, n, nd, base, inst, sizeL, keep_lists=False):
-    """The parent path's rows.  For sizeL = 0 the batched sampler writes
-    nothing, and the rows are defined on all-zero tables."""
-    lists, counts = engine.sample_check_batched(n, base, inst, sizeL)
-    if sizeL == 0:
-        for t in (counts.H, counts.C, counts.P):
-            t.zero_()
-    rows = engine.protocol_batched(n, nd, base, counts).cpu().numpy()
-    rows.setflags(write=False)
-    return (rows, lists) if keep_lists else rows
 
 
 @pytest.fixture(scope="module")

@@ -70,6 +70,10 @@ template <int NP>
 int qba_launch_mc_curve(qba_ctx *ctx, const QbaMcCurve &M);
 template <int NP>
 void qba_mc_curve_shape_n(int *waves, int64_t *lds, int *wgs);
+// qba_montecarlo_program_shape (qba_mc_kern.h); the program of NP is compiled
+template <int NP>
+int qba_mc_program_shape_n(qba_ctx *ctx, int curve, int *sampler, int *waves_compiled, int *waves_run, int64_t *lds,
+                           int *wgs);
 // QBA_BUILD_EXPERIMENT_FLAGS of the per-n object (qba_build_flags ORs them)
 template <int NP>
 int qba_lists_build_flags();

@@ -133,6 +133,19 @@ extern "C" int qba_montecarlo_shape(int n, int *waves, int64_t *lds_bytes, int *
   });
 }
 
+extern "C" int qba_montecarlo_program_shape(qba_ctx *ctx, int n, int curve, int *sampler, int *waves_compiled,
+                                            int *waves_run, int64_t *lds_bytes, int *wgs_per_cu) {
+  const char *who = "qba_montecarlo_program_shape";
+  if (n < 1 || n > QBA_MAX_PARTIES || !sampler || !waves_compiled || !waves_run || !lds_bytes || !wgs_per_cu)
+    return qba_fail(QBA_EINVAL, std::string(who) + ": n_parties must be in [1, 15] and the outputs not NULL");
+  if (!ctx) return qba_fail(QBA_EINVAL, std::string(who) + ": ctx is NULL");
+  if (int rc = need_program(ctx, n, who)) return rc;
+  return with_n(n, [&](auto k) {
+    return qba_mc_program_shape_n<decltype(k)::value>(ctx, curve, sampler, waves_compiled, waves_run, lds_bytes,
+                                                      wgs_per_cu);
+  });
+}
+
 // Launches of at most QBA_CHUNK entries (32-bit in-kernel offsets, u32 bins)
 // that never cross a multiple of 2^33 entries (inside a launch the high word
 // of the Philox pair counter e >> 1 is constant: qba_sample_quad keeps it in

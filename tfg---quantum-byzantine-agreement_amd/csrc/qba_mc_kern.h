@@ -55,13 +55,14 @@ __host__ __device__ constexpr QbaMcShape qba_mc_shape(size_t tables, int G, int 
 }
 
 // Table bytes the per-n wave count is compiled for: the closed-form stage
-// tables, else the canonical program's (uniform byte factors).  A program with
-// larger tables runs fewer waves of the same kernel (qba_launch_mc).
+// tables, else the canonical program's (uniform byte factors, the last of
+// LASTB bits, and the Q factor: table_lds of that program).  A program with
+// tables of another size may run fewer waves of the same kernel (qba_launch_mc).
 template <int NP, int SAMP>
 constexpr size_t qba_mc_tables() {
   using C = QCfg<NP>;
   if (SAMP == QBA_S_CLOSED) return (size_t)((CF<NP>::WORDS + 3) & ~3) * sizeof(uint32_t);
-  return (size_t)((C::NFB * 256 + C::W + 1) & ~1) * sizeof(uint64_t);
+  return (size_t)(((C::NFB - 1) * 256 + (1 << C::LASTB) + C::W + 1) & ~1) * sizeof(uint64_t);
 }
 template <int NP, int SAMP>
 constexpr int qba_mc_waves() {
@@ -128,14 +129,21 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64, NW * 64)))
   }
 }
 
+// The shape a program with `tables` bytes of staged tables runs sampler SAMP's
+// kernel in: at most the compiled wave count (the launcher and
+// qba_montecarlo_program_shape both ask here).
+template <int NP, int SAMP>
+static QbaMcShape qba_mc_run_shape(size_t tables) {
+  return qba_mc_shape(tables, QCfg<NP>::G, QCfg<NP>::W, qba_mc_waves<NP, SAMP>());
+}
+
 // The launch of one sampler's kernel: full workgroups of its compiled wave
 // count, of which nw_run work; persistent over the instances.
 template <int NP, int SAMP>
 static int qba_launch_mc_s(qba_ctx *ctx, const QbaMc &M, size_t tables) {
-  using C = QCfg<NP>;
   constexpr int NW = qba_mc_waves<NP, SAMP>();
   static_assert(NW >= 1, "no room for a wave beside the tables");
-  const QbaMcShape sh = qba_mc_shape(tables, C::G, C::W, NW);
+  const QbaMcShape sh = qba_mc_run_shape<NP, SAMP>(tables);
   if (sh.waves < 1) return qba_fail(QBA_EUNSUPPORTED, "qba_montecarlo_sampled: the program's tables leave no LDS for a wave");
   const void *kern = (const void *)qba_k_mc_sampled<NP, SAMP, NW>;
   if (int rc = lds_allow(kern, sh.lds)) return rc;
@@ -149,18 +157,28 @@ static int qba_launch_mc_s(qba_ctx *ctx, const QbaMc &M, size_t tables) {
   return QBA_OK;
 }
 
-template <int NP>
-int qba_launch_mc(qba_ctx *ctx, const QbaMc &M) {
+// f(std::integral_constant<int, SAMP>(), tables) for the program compiled for
+// NP: its sampler, as qba_launch_batched chooses it, and the bytes of its
+// staged tables.
+template <int NP, class F>
+static int qba_mc_with_program(qba_ctx *ctx, const F &f) {
   const QbaProgramSet *hs = reinterpret_cast<const QbaProgramSet *>(ctx->prog_host[NP]);
-  const int samp = sampler_of<NP>(hs);  // as qba_launch_batched chooses it
+  const int samp = sampler_of<NP>(hs);
   if (int rc = check_closed<NP>(hs)) return rc;
   const size_t tables = table_lds<NP>(hs, samp);
   if (samp == QBA_S_CLOSED) {
-    if constexpr (NP <= QBA_CLOSED_MAX_N) return qba_launch_mc_s<NP, QBA_S_CLOSED>(ctx, M, tables);
+    if constexpr (NP <= QBA_CLOSED_MAX_N) return f(std::integral_constant<int, QBA_S_CLOSED>(), tables);
     return qba_fail(QBA_EUNSUPPORTED, "closed form beyond n = 11");
   }
-  if (samp == QBA_S_FAST) return qba_launch_mc_s<NP, QBA_S_FAST>(ctx, M, tables);
-  return qba_launch_mc_s<NP, QBA_S_GENERAL>(ctx, M, tables);
+  if (samp == QBA_S_FAST) return f(std::integral_constant<int, QBA_S_FAST>(), tables);
+  return f(std::integral_constant<int, QBA_S_GENERAL>(), tables);
+}
+
+template <int NP>
+int qba_launch_mc(qba_ctx *ctx, const QbaMc &M) {
+  return qba_mc_with_program<NP>(ctx, [&](auto s, size_t tables) {
+    return qba_launch_mc_s<NP, decltype(s)::value>(ctx, M, tables);
+  });
 }
 
 // The shape of the shipped programs' kernel (closed form up to n = 11, the
@@ -265,11 +283,16 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64, NW * 64)))
 }
 
 template <int NP, int SAMP>
-static int qba_launch_mc_curve_s(qba_ctx *ctx, const QbaMcCurve &M, size_t tables) {
+static QbaMcShape qba_mc_curve_run_shape(size_t tables) {  // as qba_mc_run_shape
   using C = QCfg<NP>;
+  return qba_mc_shape(tables, C::G, C::W, qba_mc_curve_waves<NP, SAMP>(), qba_mc_acc_lds(C::G, C::W));
+}
+
+template <int NP, int SAMP>
+static int qba_launch_mc_curve_s(qba_ctx *ctx, const QbaMcCurve &M, size_t tables) {
   constexpr int NW = qba_mc_curve_waves<NP, SAMP>();
   static_assert(NW >= 1, "no room for a wave beside the tables");
-  const QbaMcShape sh = qba_mc_shape(tables, C::G, C::W, NW, qba_mc_acc_lds(C::G, C::W));
+  const QbaMcShape sh = qba_mc_curve_run_shape<NP, SAMP>(tables);
   if (sh.waves < 1)
     return qba_fail(QBA_EUNSUPPORTED, "qba_montecarlo_curve_sampled: the program's tables leave no LDS for a wave");
   const void *kern = (const void *)qba_k_mc_curve_sampled<NP, SAMP, NW>;
@@ -285,16 +308,27 @@ static int qba_launch_mc_curve_s(qba_ctx *ctx, const QbaMcCurve &M, size_t table
 
 template <int NP>
 int qba_launch_mc_curve(qba_ctx *ctx, const QbaMcCurve &M) {
-  const QbaProgramSet *hs = reinterpret_cast<const QbaProgramSet *>(ctx->prog_host[NP]);
-  const int samp = sampler_of<NP>(hs);
-  if (int rc = check_closed<NP>(hs)) return rc;
-  const size_t tables = table_lds<NP>(hs, samp);
-  if (samp == QBA_S_CLOSED) {
-    if constexpr (NP <= QBA_CLOSED_MAX_N) return qba_launch_mc_curve_s<NP, QBA_S_CLOSED>(ctx, M, tables);
-    return qba_fail(QBA_EUNSUPPORTED, "closed form beyond n = 11");
-  }
-  if (samp == QBA_S_FAST) return qba_launch_mc_curve_s<NP, QBA_S_FAST>(ctx, M, tables);
-  return qba_launch_mc_curve_s<NP, QBA_S_GENERAL>(ctx, M, tables);
+  return qba_mc_with_program<NP>(ctx, [&](auto s, size_t tables) {
+    return qba_launch_mc_curve_s<NP, decltype(s)::value>(ctx, M, tables);
+  });
+}
+
+// qba_montecarlo_program_shape: what the two launchers above would run the
+// program compiled for NP in, from the same sampler choice, table bytes and
+// shape functions; launches nothing.
+template <int NP>
+int qba_mc_program_shape_n(qba_ctx *ctx, int curve, int *sampler, int *waves_compiled, int *waves_run, int64_t *lds,
+                           int *wgs) {
+  return qba_mc_with_program<NP>(ctx, [&](auto s, size_t tables) {
+    constexpr int SAMP = decltype(s)::value;
+    const QbaMcShape sh = curve ? qba_mc_curve_run_shape<NP, SAMP>(tables) : qba_mc_run_shape<NP, SAMP>(tables);
+    *sampler = SAMP;
+    *waves_compiled = curve ? qba_mc_curve_waves<NP, SAMP>() : qba_mc_waves<NP, SAMP>();
+    *waves_run = sh.waves;
+    *lds = (int64_t)sh.lds;
+    *wgs = sh.wgs;
+    return (int)QBA_OK;
+  });
 }
 
 template <int NP>

@@ -413,6 +413,20 @@ class Engine:
         call("qba_montecarlo_curve_shape", n, C.byref(waves), C.byref(lds), C.byref(wgs))
         return waves.value, lds.value, wgs.value
 
+    def montecarlo_program_shape(self, n: int, curve: bool = False) -> dict:
+        """The launch shape of the program compiled for n on this engine right
+        now (qba_montecarlo_program_shape): ``sampler`` (0 general, 1 canonical
+        tables, 2 closed form), ``waves_compiled`` and ``waves_run`` per
+        workgroup, ``lds_bytes`` of a workgroup and ``wgs_per_cu``, for
+        montecarlo_sampled or (``curve``) montecarlo_curve_sampled.  Launches
+        nothing."""
+        self._check_n(n)
+        samp, nw, run, lds, wgs = C.c_int(), C.c_int(), C.c_int(), C.c_int64(), C.c_int()
+        call("qba_montecarlo_program_shape", self.ctx, n, int(bool(curve)), C.byref(samp), C.byref(nw), C.byref(run),
+             C.byref(lds), C.byref(wgs))
+        return {"sampler": samp.value, "waves_compiled": nw.value, "waves_run": run.value, "lds_bytes": lds.value,
+                "wgs_per_cu": wgs.value}
+
     # -- (A5-A8) count mode -------------------------------------------------------
     def check_counts(self, lists: torch.Tensor, n: int, count: int,
                      counts: Optional[Counts] = None, accumulate: bool = False) -> Counts:
