@@ -338,6 +338,45 @@ QBA_API int qba_montecarlo_curve_shape(int n_parties, int *waves, int64_t *lds_b
 QBA_API int qba_montecarlo_program_shape(qba_ctx *ctx, int n_parties, int curve, int *sampler, int *waves_compiled,
                                          int *waves_run, int64_t *lds_bytes, int *wgs_per_cu);
 
+/* The result rows of the calls above reduced on the device (DESIGN.md section
+ * 13.3).  rows_dev is [n_slices][n_instances][4 + 5*(n+1)] int32, contiguous:
+ * what a curve call writes, or with n_slices == 1 a single-count call.
+ * tally_dev is [n_slices][QBA_MC_TALLY_WORDS] int64.  The call ADDS to it and
+ * never clears it (the caller zeroes it once): two calls on the halves of a
+ * row block leave the words of one call on the whole block.  Words of a slice:
+ *    0 runs (rows seen, status rows included)     1 successes (word 0 != 0)
+ *    2 rows with word 2 != 0 (an empty V_i)        3 rows with status != 0
+ *    4 bitwise OR of every status seen
+ *    5 rows with bit 1 of the dishonest mask set (a dishonest commander)
+ *    6 the successes among them
+ *    7, 8, 9 sums of accept, reject, sent over ranks 1..n
+ *   10 capture matches (below)                     11..14 reserved, untouched
+ *   15 honest decisions equal to -1                16 + v those equal to v < 16
+ * Honest: ranks 1..n whose bit in word 1 is clear.  A row with status != 0
+ * counts in words 0, 3 and 4 only, whatever its other fields hold.
+ * Capture: a row matches when a condition selected in `select` holds.  With
+ * select != 0 every matching row adds 1 to word 10; with slot = the word's
+ * value before that add, slot < capture_cap stores the row's global index
+ * inst_base + i at capture_dev[slice * capture_cap + slot], so slots continue
+ * across calls.  At most capture_cap matches in a slice: the stored set is
+ * exactly the matches, in any order; more: word 10 is still exact and the
+ * buffer holds capture_cap distinct matching indices.  With select == 0 or
+ * capture_cap == 0 nothing is stored and capture_dev may be NULL; with
+ * select == 0 word 10 does not move.
+ * Checked before ctx, else QBA_EINVAL naming the argument: 1 <= n_parties <=
+ * 15, 1 <= n_slices <= QBA_MC_CURVE_MAX, n_instances >= 0 (0 does nothing),
+ * 0 <= select <= 7, capture_cap >= 0, tally_dev not NULL, rows_dev not NULL
+ * when n_instances > 0, capture_dev not NULL when select != 0 and
+ * capture_cap > 0.  Asynchronous on `stream`, allocates and copies nothing. */
+#define QBA_MC_TALLY_WORDS 32
+#define QBA_MC_SEL_FAILED   1   /* status == 0 and success == 0 */
+#define QBA_MC_SEL_EMPTY_VI 2   /* status == 0 and word 2 != 0  */
+#define QBA_MC_SEL_STATUS   4   /* status != 0 */
+QBA_API int qba_montecarlo_tally(qba_ctx *ctx, int n_parties, const int32_t *rows_dev,
+                                 int64_t n_instances, int n_slices, uint64_t inst_base,
+                                 int64_t *tally_dev, int select, int64_t *capture_dev,
+                                 int64_t capture_cap, qba_stream stream);
+
 /* ---- (A5-A8) checks, exact-order mode (bit-exact protocol parity) --------------- */
 /* isQCorrList = {k : Li[k] != Lc[k]} (tfg.py:327) as ascending indices.
  * *count_host receives the number found; at most `cap` are written. Synchronous. */

@@ -427,6 +427,43 @@ class Engine:
         return {"sampler": samp.value, "waves_compiled": nw.value, "waves_run": run.value, "lds_bytes": lds.value,
                 "wgs_per_cu": wgs.value}
 
+    # -- result rows reduced on the device (qba_montecarlo_tally) -------------------
+    TALLY_WORDS = 32  # QBA_MC_TALLY_WORDS
+
+    def montecarlo_tally(self, n: int, rows: torch.Tensor, tally: Optional[torch.Tensor] = None, inst_base: int = 0,
+                         select: int = 0, capture: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Adds the result rows ``rows`` -- int32 [n_inst, 4 + 5*(n+1)] of a
+        single-count call or [K, n_inst, ...] of a curve call -- to ``tally``,
+        int64 [K, 32] (a zeroed one is allocated when None), and returns it;
+        the words are montecarlo.T_*.  With ``select`` (montecarlo.SEL_* or-ed)
+        the global indices ``inst_base + i`` of the matching rows of slice j go
+        to ``capture[j]``, int64 [K, cap], at the slots word T_CAPTURE counts.
+        Nothing is cleared, so calls accumulate.  Asynchronous."""
+        self._check_n(n)
+        words = 4 + 5 * (n + 1)
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() not in (2, 3) or \
+                rows.shape[-1] != words or not rows.is_contiguous() or rows.device != self.device:
+            raise QbaError(f"rows must be a contiguous int32 [n_inst, {words}] or [K, n_inst, {words}] device tensor")
+        k, n_inst = (1, rows.shape[0]) if rows.dim() == 2 else (rows.shape[0], rows.shape[1])
+        if not 1 <= k <= self.CURVE_MAX:
+            raise QbaError(f"between 1 and {self.CURVE_MAX} slices, not {k}")
+        if not 0 <= int(select) <= 7:
+            raise QbaError("select is an or of montecarlo.SEL_FAILED, SEL_EMPTY_VI and SEL_STATUS")
+        if tally is None:
+            tally = torch.zeros((k, self.TALLY_WORDS), dtype=torch.int64, device=self.device)
+        if not isinstance(tally, torch.Tensor) or tally.dtype != torch.int64 or \
+                tuple(tally.shape) != (k, self.TALLY_WORDS) or not tally.is_contiguous() or tally.device != self.device:
+            raise QbaError(f"tally must be a contiguous int64 [{k}, {self.TALLY_WORDS}] device tensor")
+        cap = 0
+        if capture is not None:
+            if not isinstance(capture, torch.Tensor) or capture.dtype != torch.int64 or capture.dim() != 2 or \
+                    capture.shape[0] != k or not capture.is_contiguous() or capture.device != self.device:
+                raise QbaError(f"capture must be a contiguous int64 [{k}, cap] device tensor")
+            cap = capture.shape[1]
+        call("qba_montecarlo_tally", self.ctx, n, _ptr(rows), n_inst, k, int(inst_base) & ((1 << 64) - 1), _ptr(tally),
+             int(select), _ptr(capture) if cap else None, cap, self.stream())
+        return tally
+
     # -- (A5-A8) count mode -------------------------------------------------------
     def check_counts(self, lists: torch.Tensor, n: int, count: int,
                      counts: Optional[Counts] = None, accumulate: bool = False) -> Counts:

@@ -196,6 +196,103 @@ def summarize(n: int, out: np.ndarray) -> dict:
             "decisions": {int(v): int(c) for v, c in zip(vals, cnt)}}
 
 
+# The tally of a block of rows (qba_montecarlo_tally, qba.h): int64 words per slice.
+TALLY_WORDS = 32
+(T_RUNS, T_SUCCESSES, T_EMPTY_VI, T_STATUS_ROWS, T_STATUS_OR, T_CMD_DISHONEST, T_CMD_DISHONEST_OK, T_ACCEPT, T_REJECT,
+ T_SENT, T_CAPTURE) = range(11)
+T_DEC_NEG, T_DEC0 = 15, 16     # honest decisions equal to -1; equal to v at T_DEC0 + v, 0 <= v < 16
+SEL_FAILED, SEL_EMPTY_VI, SEL_STATUS = 1, 2, 4
+
+
+def tally_host(n: int, rows, inst_base: int = 0, select: int = 0):
+    """The specification of qba_montecarlo_tally in numpy: rows int32 [n_inst,
+    out_words(n)] or [K, n_inst, out_words(n)].  Returns ``(tally, matches)``:
+    the words the call adds to a zeroed tally, int64 [K, TALLY_WORDS], and per
+    slice the sorted global indices ``inst_base + i`` of all rows that
+    ``select`` matches (the device keeps at most its buffer's capacity of
+    them).  A row with a nonzero status counts in T_RUNS, T_STATUS_ROWS and
+    T_STATUS_OR only, whatever its other fields hold."""
+    rows = np.asarray(rows)
+    if rows.ndim == 2:
+        rows = rows[None]
+    if rows.ndim != 3 or rows.shape[2] != out_words(n) or rows.dtype != np.int32:
+        raise ValueError(f"rows must be int32 [n_inst, {out_words(n)}] or [K, n_inst, {out_words(n)}]")
+    if not 0 <= select <= 7:
+        raise ValueError("select is an or of SEL_FAILED, SEL_EMPTY_VI and SEL_STATUS")
+    tally = np.zeros((rows.shape[0], TALLY_WORDS), np.int64)
+    matches = []
+    for out, t in zip(rows, tally):
+        st = out[:, 3]
+        live = out[st == 0]
+        ok, dis = live[:, 0] != 0, live[:, 1]
+        cmd = ((dis >> 1) & 1) != 0
+        per_rank = live[:, 4 + 5:].reshape(len(live), n, 5).astype(np.int64)   # ranks 1..n
+        t[T_RUNS], t[T_SUCCESSES], t[T_EMPTY_VI] = len(out), ok.sum(), np.count_nonzero(live[:, 2])
+        t[T_STATUS_ROWS] = np.count_nonzero(st)
+        t[T_STATUS_OR] = np.bitwise_or.reduce(st.astype(np.int64) & _U32) if len(st) else 0
+        t[T_CMD_DISHONEST], t[T_CMD_DISHONEST_OK] = cmd.sum(), (cmd & ok).sum()
+        t[T_ACCEPT], t[T_REJECT], t[T_SENT] = (per_rank[:, :, f].sum() for f in (2, 3, 4))
+        honest = ((dis[:, None] >> np.arange(1, n + 1)) & 1) == 0
+        dec = per_rank[:, :, 0][honest]
+        t[T_DEC_NEG] = np.count_nonzero(dec == -1)
+        t[T_DEC0:T_DEC0 + 16] = np.bincount(dec[(dec >= 0) & (dec < 16)], minlength=16)
+        hit = np.zeros(len(out), bool)
+        if select & SEL_FAILED:
+            hit |= (st == 0) & (out[:, 0] == 0)
+        if select & SEL_EMPTY_VI:
+            hit |= (st == 0) & (out[:, 2] != 0)
+        if select & SEL_STATUS:
+            hit |= st != 0
+        t[T_CAPTURE] = np.count_nonzero(hit)
+        matches.append([int(inst_base) + int(i) for i in np.nonzero(hit)[0]])
+    return tally, matches
+
+
+def summary_from_tally(n: int, tally_row) -> dict:
+    """:func:`summarize` from one slice of a tally: the same five keys with the
+    same values, then ``cmd_dishonest_runs``, ``cmd_dishonest_successes`` and
+    the sums ``accept``, ``reject``, ``sent`` over ranks 1..n.  QbaError when
+    rows ended with a nonzero status."""
+    t = [int(x) for x in np.asarray(tally_row).reshape(TALLY_WORDS)]
+    if t[T_STATUS_ROWS]:
+        raise QbaError(f"{t[T_STATUS_ROWS]} instance(s) ended with a nonzero status "
+                       f"(the or of their statuses: {t[T_STATUS_OR]})")
+    runs, ok = t[T_RUNS], t[T_SUCCESSES]
+    dec = {v - T_DEC0: t[v] for v in range(T_DEC_NEG, T_DEC0 + 16) if t[v]}
+    return {"runs": runs, "successes": ok, "rate": ok / runs if runs else 0.0, "empty_vi_runs": t[T_EMPTY_VI],
+            "decisions": dec, "cmd_dishonest_runs": t[T_CMD_DISHONEST],
+            "cmd_dishonest_successes": t[T_CMD_DISHONEST_OK], "accept": t[T_ACCEPT], "reject": t[T_REJECT],
+            "sent": t[T_SENT]}
+
+
+def _tallied(n: int, k: int, runs: int, batch: int, failures: int, engine, decide) -> list:
+    """The summaries of ``k`` slices with the rows tallied on the device:
+    ``decide(off, b, out)`` writes the rows of instances [off, off + b) into
+    ``out`` ([k, b, words], or [b, words] when k == 1); one row buffer of
+    ``batch`` instances serves every batch, and only the [k, 32] tally (and the
+    [k, failures] captured indices) come to the host."""
+    import torch
+    if failures < 0:
+        raise ValueError("failures >= 0")
+    dev = engine.device
+    tally = torch.zeros((k, TALLY_WORDS), dtype=torch.int64, device=dev)
+    capture = torch.zeros((k, failures), dtype=torch.int64, device=dev) if failures else None
+    buf = torch.empty((k, min(batch, runs), out_words(n)), dtype=torch.int32, device=dev) if runs else None
+    for off in range(0, runs, batch):
+        b = min(batch, runs - off)
+        out = buf if b == buf.shape[1] else buf.view(-1)[:k * b * out_words(n)].view(k, b, out_words(n))
+        decide(off, b, out)
+        engine.montecarlo_tally(n, out, tally, inst_base=off, select=SEL_FAILED if failures else 0, capture=capture)
+    host = tally.cpu().numpy()
+    res = [summary_from_tally(n, row) for row in host]
+    if failures:
+        cap = capture.cpu().numpy()
+        for j, s in enumerate(res):
+            s["failed_total"] = int(host[j, T_CAPTURE])
+            s["failed_runs"] = sorted(int(i) for i in cap[j, :min(failures, s["failed_total"])])
+    return res
+
+
 def _nq(n: int) -> int:
     return int(n).bit_length()  # ceil(log2(n + 1)), tfg.py:317
 
@@ -261,7 +358,7 @@ def masks_from_lists(n: int, lists) -> dict:
 
 
 def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, packed: bool = True,
-        batch: int = 4096, path: str = "tables") -> dict:
+        batch: int = 4096, path: str = "tables", tally: bool = False, failures: int = 0) -> dict:
     """``runs`` independent instances on the device, ``batch`` at a time, batch
     at offset ``off`` under key ``seed + off``; only the result rows are copied
     to the host.  Returns :func:`summarize` of all rows.
@@ -270,12 +367,33 @@ def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, pack
     protocol_batched; the list buffer is reused across batches.
     ``path="fused"``: one montecarlo_sampled call per batch -- the same
     instances and rows, with no list buffer and no count tables (``packed``
-    has nothing to apply to)."""
+    has nothing to apply to).
+
+    ``tally=True`` (implied by ``failures > 0``): the rows stay on the device,
+    in one buffer of ``batch`` instances, and montecarlo_tally reduces each
+    batch there; the result is :func:`summary_from_tally`, whose memory does
+    not grow with ``runs``.  ``failures=F`` adds ``failed_runs``, the sorted
+    indices of up to F runs without success (run i has key ``seed + i``), and
+    ``failed_total``, how many there were."""
     import torch
     if runs < 0 or batch < 1:
         raise ValueError("runs >= 0 and batch >= 1")
     if path not in ("tables", "fused"):
         raise ValueError("path is 'tables' or 'fused'")
+    if tally or failures:
+        state = {"lists": None}
+
+        def decide(off, b, out):
+            key = (int(seed) + off) & MASK64
+            if path == "fused":
+                engine.montecarlo_sampled(n, n_dishonest, key, b, sizeL, out=out[0])
+                return
+            li = state["lists"]
+            buf, counts = engine.sample_check_batched(n, key, b, sizeL, None if li is None else li[:b], packed=packed)
+            if li is None:
+                state["lists"] = buf
+            engine.protocol_batched(n, n_dishonest, key, counts, out=out[0])
+        return _tallied(n, 1, runs, batch, failures, engine, decide)[0]
     lists, outs = None, []
     for off in range(0, runs, batch):
         b = min(batch, runs - off)
@@ -304,16 +422,23 @@ def curve_host(n: int, counts, n_dishonest: int, n_inst: int, seed_base: int, en
     return np.stack(rows) if rows else np.zeros((0, n_inst, out_words(n)), np.int32)
 
 
-def curve(n: int, counts, n_dishonest: int, runs: int, seed: int, engine, batch: int = 4096) -> dict:
+def curve(n: int, counts, n_dishonest: int, runs: int, seed: int, engine, batch: int = 4096, tally: bool = False,
+          failures: int = 0) -> dict:
     """The failure curve over sizeL: ``runs`` instances, ``batch`` at a time as
     :func:`run` keys them, each decided at every sizeL of the strictly
     increasing ``counts`` by one montecarlo_curve_sampled call per batch.
     Returns ``{sizeL: summarize(...)}`` in checkpoint order; the summary at
-    sizeL = c is that of ``run(n, c, ..., path="fused")``."""
+    sizeL = c is that of ``run(n, c, ..., path="fused")``.  ``tally`` and
+    ``failures`` as in :func:`run`, per checkpoint."""
     import torch
     if runs < 0 or batch < 1:
         raise ValueError("runs >= 0 and batch >= 1")
     counts = [int(c) for c in counts]
+    if tally or failures:
+        def decide(off, b, out):
+            engine.montecarlo_curve_sampled(n, n_dishonest, (int(seed) + off) & MASK64, b, counts, out=out)
+        engine._check_curve(n, n_dishonest, runs, counts)
+        return dict(zip(counts, _tallied(n, len(counts), runs, batch, failures, engine, decide)))
     outs = []
     for off in range(0, runs, batch):
         b = min(batch, runs - off)

@@ -69,6 +69,12 @@ def _args(argv):
                     help="with --runs: decide every instance at each of these sizeL and at the positional sizeL in "
                          "one pass per batch (montecarlo.curve; at most 32 in all); one summary line per sizeL, "
                          "increasing; implies --fused")
+    ap.add_argument("--tally", action="store_true",
+                    help="with --runs: reduce each batch's result rows on the device (montecarlo.run tally=True); the "
+                         "same summary lines, from device memory that does not grow with --runs")
+    ap.add_argument("--failures", type=int, default=0, metavar="K",
+                    help="with --runs: after each summary line, the indices of up to K runs without success, to "
+                         "replay under key seed + index; implies --tally")
     ap.add_argument("--quiet", action="store_true", help="print only the outcome")
     ap.add_argument("--timing", action="store_true", help="print the wall time of the run")
     ap.add_argument("--wire", action="store_true",
@@ -83,6 +89,10 @@ def _args(argv):
             ap.error(f"--curve: at most {CURVE_MAX} checkpoints (the positional sizeL included), not {len(a.curve)}")
         if a.curve[0] < 0 or a.curve[-1] >= 1 << 31:
             ap.error("--curve: every sizeL must be in [0, 2^31)")
+    if a.failures < 0:
+        ap.error("--failures: K >= 0")
+    if (a.tally or a.failures) and a.runs is None:
+        ap.error("--tally and --failures need --runs")
     return a
 
 
@@ -202,14 +212,18 @@ def _montecarlo(a, eng, size_l) -> int:
     from . import montecarlo
     seed = secrets.randbits(62) if a.seed is None else a.seed
     t0 = time.perf_counter()
+    how = {"tally": True, "failures": a.failures} if a.tally or a.failures else {}
     if a.curve is not None:
-        points = montecarlo.curve(a.parties, a.curve, a.nDishonest, a.runs, seed, eng, batch=a.batch)
+        points = montecarlo.curve(a.parties, a.curve, a.nDishonest, a.runs, seed, eng, batch=a.batch, **how)
     else:
         points = {size_l: montecarlo.run(a.parties, size_l, a.nDishonest, a.runs, seed, eng, batch=a.batch,
-                                         path="fused" if a.fused else "tables")}
+                                         path="fused" if a.fused else "tables", **how)}
     for c, s in points.items():
         print(f"Runs: {s['runs']} Successes: {s['successes']} Rate: {s['rate']:.6f} "
               f"(n={a.parties}, sizeL={c}, dishonest={a.nDishonest}, empty-V_i runs={s['empty_vi_runs']})")
+        if a.failures:
+            print(f"Failed runs ({len(s['failed_runs'])} of {s['failed_total']}, key = seed + index, seed={seed}): "
+                  + " ".join(str(i) for i in s["failed_runs"]))
     if a.timing:
         print(f"wall {time.perf_counter() - t0:.3f} s ({a.runs} instances on the device)")
     return 0

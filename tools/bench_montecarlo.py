@@ -19,7 +19,12 @@ instances x n = 7 x sizeL = 1e5, 2 dishonest, on one GPU.
       same counts, the K timed as one interval; the rows of the two are compared
       at the timed shape.  One JSON line per --curve; nothing else is measured.
 
-(a), (b), (d) and the --curve pair are device-event times of single calls on warm code: median, min
+  --tally  another mode, per --sizeL: montecarlo_tally alone (with and without
+      capturing failed runs), montecarlo_sampled followed by it, and as host
+      wall time the two endings of a batch: tally + one [1, 32] copy +
+      summary_from_tally against rows to host + summarize.
+
+(a), (b), (d), the --tally calls and the --curve pair are device-event times of single calls on warm code: median, min
 and max over --repeats launches after --warmup launches.  (c) is host wall
 time around runs that end in device synchronisation (each reads its tables
 back).  Prints one JSON line; --out also writes it to a file.  No GPU: fails.
@@ -66,10 +71,15 @@ def main(argv=None) -> int:
     ap.add_argument("--out", type=Path, default=None)
     ap.add_argument("--curve", action="append", default=None, metavar="C0,C1,...",
                     help="time one curve call against the separate calls at these counts; repeatable")
+    ap.add_argument("--tally", action="store_true",
+                    help="time montecarlo_tally alone, montecarlo_sampled followed by it, and the rows-to-host "
+                         "ending it replaces, at each --sizeL; nothing else is measured")
     a = ap.parse_args(argv)
 
     eng = importlib.import_module(f"{PKG}.engine").Engine(0)
-    if a.curve:
+    if a.tally:
+        lines = [json.dumps(_measure_tally(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
+    elif a.curve:
         lines = [json.dumps(_measure_curve(a, eng, sorted({int(c) for c in text.split(",")}))) for text in a.curve]
     else:
         lines = [json.dumps(_measure(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
@@ -108,6 +118,63 @@ def _measure_curve(a, eng, counts) -> dict:
     # faster only where the min-max ranges do not overlap
     res["curve_faster"] = c["max_ms"] < s["min_ms"]
     res["separate_faster"] = s["max_ms"] < c["min_ms"]
+    return res
+
+
+def _walls(fn, warmup, repeats):
+    """Host wall time of calls that end synchronised (they read results back)."""
+    import torch
+    for _ in range(warmup):
+        fn()
+    ms = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        ms.append(1e3 * (time.perf_counter() - t0))
+    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "calls": repeats}
+
+
+def _measure_tally(a, eng, size_l) -> dict:
+    """--tally: the ending of a Monte-Carlo batch both ways, on the fused path."""
+    import torch
+    mc = importlib.import_module(f"{PKG}.montecarlo")
+    n, nd, inst = a.parties, a.dishonest, a.instances
+    rows = eng.montecarlo_sampled(n, nd, a.seed, inst, size_l)
+    tally = torch.zeros((1, mc.TALLY_WORDS), dtype=torch.int64, device=eng.device)
+    capture = torch.zeros((1, 64), dtype=torch.int64, device=eng.device)
+
+    def decide_and_tally():
+        eng.montecarlo_sampled(n, nd, a.seed, inst, size_l, rows)
+        eng.montecarlo_tally(n, rows, tally)
+
+    def ending_tally():
+        tally.zero_()
+        decide_and_tally()
+        return mc.summary_from_tally(n, tally.cpu().numpy()[0])
+
+    def ending_rows():
+        eng.montecarlo_sampled(n, nd, a.seed, inst, size_l, rows)
+        return mc.summarize(n, rows.cpu().numpy())
+
+    want = ending_rows()
+    got = ending_tally()
+    res = {"config": {"n": n, "sizeL": size_l, "dishonest": nd, "instances": inst, "seed": a.seed,
+                      "device": torch.cuda.get_device_name(0), "row_bytes": int(rows.numel()) * 4},
+           "result": {k: want[k] for k in ("runs", "successes", "rate", "empty_vi_runs")},
+           "summaries_equal": all(got[k] == want[k] for k in want)}
+    # device-event times of the asynchronous calls
+    res["decision_montecarlo_sampled"] = _events(lambda: eng.montecarlo_sampled(n, nd, a.seed, inst, size_l, rows),
+                                                 a.warmup, a.repeats)
+    res["tally_alone"] = _events(lambda: eng.montecarlo_tally(n, rows, tally), a.warmup, a.repeats)
+    res["tally_alone_capturing_failed"] = _events(
+        lambda: eng.montecarlo_tally(n, rows, tally, select=mc.SEL_FAILED, capture=capture), a.warmup, a.repeats)
+    res["decision_plus_tally"] = _events(decide_and_tally, a.warmup, a.repeats)
+    res["tally_over_decision_at_median"] = (res["tally_alone"]["median_ms"] /
+                                            res["decision_montecarlo_sampled"]["median_ms"])
+    # host wall times of the two endings, result on the host
+    res["wall_decision_tally_summary"] = _walls(ending_tally, a.warmup, a.repeats)
+    res["wall_decision_rows_to_host_summarize"] = _walls(ending_rows, a.warmup, a.repeats)
     return res
 
 

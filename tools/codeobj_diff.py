@@ -3,11 +3,16 @@
 
     tools/codeobj_diff.py OLD/libqba.so NEW/libqba.so
 
-For every gfx950 code object (in link order) the sections .text (the code),
+Code objects are paired by position (link order) when both builds have the
+same number, else by their first kernel symbol, so that a source file added
+to or taken out of the build shows as one `added` / `removed` object and the
+others are still compared.  For every pair the sections .text (the code),
 .rodata (the kernel descriptors) and .note (the kernel metadata) must be
 byte-identical and the sets of kernel symbols (*.kd) equal.  Symbol-name
 tables are not compared: each object's __hip_cuid_* name hashes its source.
-Prints one line per object; exit status 1 on any difference.  No GPU needed.
+Prints one line per object; exit status 1 on any difference between paired
+objects or on a removed one (an added object alone is not a difference in
+the kernels the old build had).  No GPU needed.
 """
 import hashlib
 import sys
@@ -24,22 +29,40 @@ def summary(elf: bytes):
     return secs, frozenset(_descriptors(elf))
 
 
+def _line(i, secs, kernels, verdict):
+    first = min(kernels, default="(no kernels)")
+    text = secs.get(".text", b"")
+    return (f"object {i:2d}: {len(kernels):3d} kernels, .text {len(text):8d} B "
+            f"sha256 {hashlib.sha256(text).hexdigest()[:12]}  {verdict}  [{first[:40]}]")
+
+
 def main(old: str, new: str) -> int:
-    a, b = list(code_objects(old)), list(code_objects(new))
-    bad = len(a) != len(b)
-    if bad:
-        print(f"DIFFERENT: {len(a)} code objects against {len(b)}")
-    for i, (x, y) in enumerate(zip(a, b)):
-        (sx, kx), (sy, ky) = summary(x), summary(y)
+    a, b = [summary(x) for x in code_objects(old)], [summary(y) for y in code_objects(new)]
+    if len(a) == len(b):
+        pairs = list(zip(a, b))
+    else:
+        by_first = {min(k, default=""): (s, k) for s, k in a}
+        pairs = [(by_first.pop(min(k, default=""), None), (s, k)) for s, k in b]
+        pairs += [(x, None) for x in by_first.values()]
+    bad = False
+    for i, (x, y) in enumerate(pairs):
+        if x is None:
+            print(_line(i, *y, "added"))
+            continue
+        if y is None:
+            print(_line(i, *x, "REMOVED"))
+            bad = True
+            continue
+        (sx, kx), (sy, ky) = x, y
         diff = [n for n in SECTIONS if sx.get(n) != sy.get(n)]
         if kx != ky:
             diff.append(f"kernels -{len(kx - ky)} +{len(ky - kx)}")
         bad |= bool(diff)
-        first = min(ky, default="(no kernels)")
-        print(f"object {i:2d}: {len(ky):3d} kernels, .text {len(sy.get('.text', b'')):8d} B "
-              f"sha256 {hashlib.sha256(sy.get('.text', b'')).hexdigest()[:12]}  "
-              f"{'DIFFERENT: ' + ', '.join(diff) if diff else 'equal'}  [{first[:40]}]")
-    print("DIFFERENT" if bad else f"all {len(b)} code objects equal (.text, .rodata, .note, kernel names)")
+        print(_line(i, sy, ky, "DIFFERENT: " + ", ".join(diff) if diff else "equal"))
+    added = sum(1 for x, _ in pairs if x is None)
+    print("DIFFERENT" if bad else
+          f"all {len(a)} code objects of the old build equal (.text, .rodata, .note, kernel names)"
+          + (f"; {added} added" if added else ""))
     return 1 if bad else 0
 
 
