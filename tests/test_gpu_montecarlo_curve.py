@@ -151,6 +151,24 @@ def test_lists_form_on_the_devices_own_sampled_rows(engine, single):
                lambda c: got[counts.index(c)], counts, "curve sampled:")
 
 
+def test_lists_form_second_launch_chunk(engine):
+    """More than 2^20 instances: the second launch of qba_montecarlo_curve_lists,
+    where the kernel adds its chunk's first instance to blockIdx.x.  Row i of
+    a slice depends on key base + i and instance i's lists alone, so the rows
+    across the chunk boundary are those of a small call from there on."""
+    import torch
+    n, nd, counts, base = 2, 1, [2, 4], 0xC0FFEE
+    cut, inst = 2**20 - 2, 2**20 + 3
+    gen = torch.Generator(device=engine.device).manual_seed(20)
+    lists = torch.randint(0, 4, (inst, n + 1, counts[-1]), dtype=torch.uint8, device=engine.device, generator=gen)
+    big = engine.montecarlo_curve_lists(n, nd, base, lists, counts)[:, cut:].cpu().numpy()
+    small = engine.montecarlo_curve_lists(n, nd, base + cut, lists[cut:], counts).cpu().numpy()
+    _eq_slices(big, lambda c: small[counts.index(c)], counts)
+    assert not big[:, :, 3].any()
+    for rows in big:
+        assert any(not np.array_equal(rows[0], r) for r in rows[1:])
+
+
 def test_range_status_from_the_checkpoint_after_the_plant_on(engine):
     mc = sub("montecarlo")
     case = next(c for c in HOSTILE if c["n"] == 3)

@@ -206,6 +206,24 @@ def test_out_is_written_in_every_word_and_checked(engine):
         engine.montecarlo_sampled(n, nd, base, inst, 1 << 31)
 
 
+def test_lists_form_second_launch_chunk(engine):
+    """More than 2^20 instances: the second launch of qba_montecarlo_lists,
+    where the kernel adds its chunk's first instance to blockIdx.x.  Row i
+    depends on key base + i and instance i's lists alone, so the rows across
+    the chunk boundary are those of a small call from there on (which the
+    tests above hold to run_host)."""
+    import torch
+    n, nd, count, base = 2, 1, 4, 0xC0FFEE
+    cut, inst = 2**20 - 2, 2**20 + 3
+    gen = torch.Generator(device=engine.device).manual_seed(20)
+    lists = torch.randint(0, 4, (inst, n + 1, count), dtype=torch.uint8, device=engine.device, generator=gen)
+    big = engine.montecarlo_lists(n, nd, base, lists, count)[cut:].cpu().numpy()
+    small = engine.montecarlo_lists(n, nd, base + cut, lists[cut:], count).cpu().numpy()
+    _eq(big, small)
+    assert not big[:, 3].any()
+    assert any(not np.array_equal(big[0], r) for r in big[1:])
+
+
 def test_batches_split_points_and_streams(engine):
     import torch
     mc = sub("montecarlo")

@@ -210,7 +210,7 @@ def test_curve_batches_and_rejects_like_run():
     class Fake:
         calls = []
 
-        def montecarlo_curve_sampled(self, n, nd, key, b, counts):
+        def montecarlo_curve_sampled(self, n, nd, key, b, counts, out=None):
             import torch
             self.calls.append((key, b, list(counts)))
             rows = torch.zeros((len(counts), b, mc.out_words(n)), dtype=torch.int32)

@@ -252,15 +252,18 @@ int qba_ensure_staging(qba_ctx *ctx, size_t host_bytes, size_t dev_bytes);
 #define QBA_ZC_MAX (1u << 20)
 int qba_ensure_zc(qba_ctx *ctx, size_t bytes);
 int qba_set_device(qba_ctx *ctx);
-// The argument envelope of qba_montecarlo_sampled / _lists (qba_proto.hip)
-int qba_mc_check(const char *who, qba_ctx *ctx, int n, int n_dis, int64_t n_inst, uint64_t count, const void *out);
+// The argument envelope of the qba_montecarlo_* calls (qba_proto.hip):
+// n_parties and n_dishonest, then `bad_count` (what is wrong with the count or
+// the checkpoints, NULL when nothing is), then ctx, n_instances and out
+int qba_mc_check(const char *who, qba_ctx *ctx, int n, int n_dis, const char *bad_count, int64_t n_inst,
+                 const void *out);
 // The checkpoints of a curve call, by value in the kernel arguments
 struct QbaMcCounts {
   uint32_t c[QBA_MC_CURVE_MAX];
   int n;
 };
-// The envelope of qba_montecarlo_curve_sampled / _lists: n_parties, n_dishonest
-// and the checkpoint list before ctx; fills `cv`
+// That envelope for qba_montecarlo_curve_sampled / _lists, `bad_count` being
+// the checks of the checkpoint list; fills `cv`
 int qba_mc_curve_check(const char *who, qba_ctx *ctx, int n, int n_dis, int64_t n_inst, const uint32_t *counts,
                        int n_counts, const void *out, QbaMcCounts *cv);
 

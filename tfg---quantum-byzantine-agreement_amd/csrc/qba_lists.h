@@ -33,19 +33,11 @@ struct QbaBatch {
   int packed;  // nibble rows: ld / inst_stride in bytes of packed rows
 };
 
-// qba_montecarlo_sampled (qba_mc_kern.h); fields have the kernel arguments' types
+// qba_montecarlo_sampled and qba_montecarlo_curve_sampled (qba_mc_kern.h);
+// fields have the kernel arguments' types.  The single-count call is the one
+// with one checkpoint and `curve` 0, which picks its kernel.
 struct QbaMc {
-  const QbaProgramSet *ps;
-  uint64_t seed_base;
-  int64_t n_inst;
-  uint64_t count;
-  int n_dis;
-  int32_t *out;
-  hipStream_t stream;
-};
-
-// qba_montecarlo_curve_sampled (qba_mc_kern.h); as QbaMc
-struct QbaMcCurve {
+  const char *who;  // the exported function, for messages
   const QbaProgramSet *ps;
   uint64_t seed_base;
   int64_t n_inst;
@@ -53,6 +45,7 @@ struct QbaMcCurve {
   int32_t *out;
   hipStream_t stream;
   QbaMcCounts counts;
+  int curve;
 };
 
 template <int NP>
@@ -64,12 +57,9 @@ template <int NP>
 int qba_launch_batched(qba_ctx *ctx, const QbaBatch &B);
 template <int NP>
 int qba_launch_mc(qba_ctx *ctx, const QbaMc &M);
+// qba_montecarlo_shape, or (curve) qba_montecarlo_curve_shape
 template <int NP>
-void qba_mc_shape_n(int *waves, int64_t *lds, int *wgs);
-template <int NP>
-int qba_launch_mc_curve(qba_ctx *ctx, const QbaMcCurve &M);
-template <int NP>
-void qba_mc_curve_shape_n(int *waves, int64_t *lds, int *wgs);
+void qba_mc_shape_n(int curve, int *waves, int64_t *lds, int *wgs);
 // qba_montecarlo_program_shape (qba_mc_kern.h); the program of NP is compiled
 template <int NP>
 int qba_mc_program_shape_n(qba_ctx *ctx, int curve, int *sampler, int *waves_compiled, int *waves_run, int64_t *lds,

@@ -91,46 +91,47 @@ extern "C" int qba_sample_check_batched_packed(qba_ctx *ctx, int n, uint64_t see
                  "qba_sample_check_batched_packed");
 }
 
+// The two sampled calls behind their envelopes: M holds the checkpoints
+static int mc_sampled(qba_ctx *ctx, int n, QbaMc &M) {
+  if (int rc = need_program(ctx, n, M.who)) return rc;
+  if (M.n_inst == 0) return QBA_OK;
+  if (int rc = qba_set_device(ctx)) return rc;
+  M.ps = (const QbaProgramSet *)ctx->prog_dev[n];
+  return with_n(n, [&](auto k) { return qba_launch_mc<decltype(k)::value>(ctx, M); });
+}
+
 extern "C" int qba_montecarlo_sampled(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
                                       uint64_t count, int32_t *out, qba_stream stream) {
-  int rc = qba_mc_check("qba_montecarlo_sampled", ctx, n, n_dis, n_inst, count, out);
-  if (rc) return rc;
-  if ((rc = need_program(ctx, n, "qba_montecarlo_sampled"))) return rc;
-  if (n_inst == 0) return QBA_OK;
-  if ((rc = qba_set_device(ctx))) return rc;
-  QbaMc M{(const QbaProgramSet *)ctx->prog_dev[n], seed_base, n_inst, count, n_dis, out, (hipStream_t)stream};
-  return with_n(n, [&](auto k) { return qba_launch_mc<decltype(k)::value>(ctx, M); });
+  const char *who = "qba_montecarlo_sampled";
+  QbaMc M{who, nullptr, seed_base, n_inst, n_dis, out, (hipStream_t)stream, {{(uint32_t)count}, 1}, 0};
+  if (int rc = qba_mc_check(who, ctx, n, n_dis, count >> 31 ? "count must be < 2^31" : nullptr, n_inst, out)) return rc;
+  return mc_sampled(ctx, n, M);
 }
 
 extern "C" int qba_montecarlo_curve_sampled(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
                                             const uint32_t *counts, int n_counts, int32_t *out,
                                             qba_stream stream) {
-  QbaMcCurve M{nullptr, seed_base, n_inst, n_dis, out, (hipStream_t)stream, {}};
-  int rc = qba_mc_curve_check("qba_montecarlo_curve_sampled", ctx, n, n_dis, n_inst, counts, n_counts, out, &M.counts);
-  if (rc) return rc;
-  if ((rc = need_program(ctx, n, "qba_montecarlo_curve_sampled"))) return rc;
-  if (n_inst == 0) return QBA_OK;
-  if ((rc = qba_set_device(ctx))) return rc;
-  M.ps = (const QbaProgramSet *)ctx->prog_dev[n];
-  return with_n(n, [&](auto k) { return qba_launch_mc_curve<decltype(k)::value>(ctx, M); });
+  const char *who = "qba_montecarlo_curve_sampled";
+  QbaMc M{who, nullptr, seed_base, n_inst, n_dis, out, (hipStream_t)stream, {}, 1};
+  if (int rc = qba_mc_curve_check(who, ctx, n, n_dis, n_inst, counts, n_counts, out, &M.counts)) return rc;
+  return mc_sampled(ctx, n, M);
+}
+
+static int mc_shape(const char *who, int n, int curve, int *waves, int64_t *lds_bytes, int *wgs_per_cu) {
+  if (n < 1 || n > QBA_MAX_PARTIES || !waves || !lds_bytes || !wgs_per_cu)
+    return qba_fail(QBA_EINVAL, std::string(who) + ": n_parties must be in [1, 15] and the outputs not NULL");
+  return with_n(n, [&](auto k) {
+    qba_mc_shape_n<decltype(k)::value>(curve, waves, lds_bytes, wgs_per_cu);
+    return (int)QBA_OK;
+  });
 }
 
 extern "C" int qba_montecarlo_curve_shape(int n, int *waves, int64_t *lds_bytes, int *wgs_per_cu) {
-  if (n < 1 || n > QBA_MAX_PARTIES || !waves || !lds_bytes || !wgs_per_cu)
-    return qba_fail(QBA_EINVAL, "qba_montecarlo_curve_shape: n_parties must be in [1, 15] and the outputs not NULL");
-  return with_n(n, [&](auto k) {
-    qba_mc_curve_shape_n<decltype(k)::value>(waves, lds_bytes, wgs_per_cu);
-    return (int)QBA_OK;
-  });
+  return mc_shape("qba_montecarlo_curve_shape", n, 1, waves, lds_bytes, wgs_per_cu);
 }
 
 extern "C" int qba_montecarlo_shape(int n, int *waves, int64_t *lds_bytes, int *wgs_per_cu) {
-  if (n < 1 || n > QBA_MAX_PARTIES || !waves || !lds_bytes || !wgs_per_cu)
-    return qba_fail(QBA_EINVAL, "qba_montecarlo_shape: n_parties must be in [1, 15] and the outputs not NULL");
-  return with_n(n, [&](auto k) {
-    qba_mc_shape_n<decltype(k)::value>(waves, lds_bytes, wgs_per_cu);
-    return (int)QBA_OK;
-  });
+  return mc_shape("qba_montecarlo_shape", n, 0, waves, lds_bytes, wgs_per_cu);
 }
 
 extern "C" int qba_montecarlo_program_shape(qba_ctx *ctx, int n, int curve, int *sampler, int *waves_compiled,

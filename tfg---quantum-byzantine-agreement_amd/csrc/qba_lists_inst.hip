@@ -11,9 +11,7 @@
 template int qba_launch_lists<QBA_INST_N>(qba_ctx *ctx, const QbaLaunch &L);
 template int qba_launch_batched<QBA_INST_N>(qba_ctx *ctx, const QbaBatch &B);
 template int qba_launch_mc<QBA_INST_N>(qba_ctx *ctx, const QbaMc &M);
-template void qba_mc_shape_n<QBA_INST_N>(int *waves, int64_t *lds, int *wgs);
-template int qba_launch_mc_curve<QBA_INST_N>(qba_ctx *ctx, const QbaMcCurve &M);
-template void qba_mc_curve_shape_n<QBA_INST_N>(int *waves, int64_t *lds, int *wgs);
 template int qba_mc_program_shape_n<QBA_INST_N>(qba_ctx *ctx, int curve, int *sampler, int *waves_compiled,
                                                 int *waves_run, int64_t *lds, int *wgs);
+template void qba_mc_shape_n<QBA_INST_N>(int curve, int *waves, int64_t *lds, int *wgs);
 template <> int qba_lists_build_flags<QBA_INST_N>() { return QBA_BUILD_EXPERIMENT_FLAGS; }

@@ -64,11 +64,6 @@ constexpr size_t qba_mc_tables() {
   if (SAMP == QBA_S_CLOSED) return (size_t)((CF<NP>::WORDS + 3) & ~3) * sizeof(uint32_t);
   return (size_t)(((C::NFB - 1) * 256 + (1 << C::LASTB) + C::W + 1) & ~1) * sizeof(uint64_t);
 }
-template <int NP, int SAMP>
-constexpr int qba_mc_waves() {
-  return qba_mc_shape(qba_mc_tables<NP, SAMP>(), QCfg<NP>::G, QCfg<NP>::W, 16).waves;
-}
-
 template <int NP, int SAMP, int NW>
 __global__ void __attribute__((amdgpu_flat_work_group_size(64, NW * 64)))
     qba_k_mc_sampled(const QbaProgramSet *__restrict__ ps, uint64_t seed_base, int64_t n_inst, uint32_t count,
@@ -129,69 +124,6 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64, NW * 64)))
   }
 }
 
-// The shape a program with `tables` bytes of staged tables runs sampler SAMP's
-// kernel in: at most the compiled wave count (the launcher and
-// qba_montecarlo_program_shape both ask here).
-template <int NP, int SAMP>
-static QbaMcShape qba_mc_run_shape(size_t tables) {
-  return qba_mc_shape(tables, QCfg<NP>::G, QCfg<NP>::W, qba_mc_waves<NP, SAMP>());
-}
-
-// The launch of one sampler's kernel: full workgroups of its compiled wave
-// count, of which nw_run work; persistent over the instances.
-template <int NP, int SAMP>
-static int qba_launch_mc_s(qba_ctx *ctx, const QbaMc &M, size_t tables) {
-  constexpr int NW = qba_mc_waves<NP, SAMP>();
-  static_assert(NW >= 1, "no room for a wave beside the tables");
-  const QbaMcShape sh = qba_mc_run_shape<NP, SAMP>(tables);
-  if (sh.waves < 1) return qba_fail(QBA_EUNSUPPORTED, "qba_montecarlo_sampled: the program's tables leave no LDS for a wave");
-  const void *kern = (const void *)qba_k_mc_sampled<NP, SAMP, NW>;
-  if (int rc = lds_allow(kern, sh.lds)) return rc;
-  const int64_t need = (M.n_inst + sh.waves - 1) / sh.waves, cap = (int64_t)ctx->num_cus * sh.wgs;
-  const int grid = (int)(need < cap ? need : cap);
-  const uint32_t count = (uint32_t)M.count;
-  const int nw_run = sh.waves;
-  const void *args[] = {&M.ps, &M.seed_base, &M.n_inst, &count, &M.n_dis, &nw_run, &M.out};
-  QBA_HIP(hipLaunchKernel(kern, dim3(grid), dim3(NW * 64), const_cast<void **>(args), sh.lds, M.stream));
-  QBA_HIP(hipGetLastError());
-  return QBA_OK;
-}
-
-// f(std::integral_constant<int, SAMP>(), tables) for the program compiled for
-// NP: its sampler, as qba_launch_batched chooses it, and the bytes of its
-// staged tables.
-template <int NP, class F>
-static int qba_mc_with_program(qba_ctx *ctx, const F &f) {
-  const QbaProgramSet *hs = reinterpret_cast<const QbaProgramSet *>(ctx->prog_host[NP]);
-  const int samp = sampler_of<NP>(hs);
-  if (int rc = check_closed<NP>(hs)) return rc;
-  const size_t tables = table_lds<NP>(hs, samp);
-  if (samp == QBA_S_CLOSED) {
-    if constexpr (NP <= QBA_CLOSED_MAX_N) return f(std::integral_constant<int, QBA_S_CLOSED>(), tables);
-    return qba_fail(QBA_EUNSUPPORTED, "closed form beyond n = 11");
-  }
-  if (samp == QBA_S_FAST) return f(std::integral_constant<int, QBA_S_FAST>(), tables);
-  return f(std::integral_constant<int, QBA_S_GENERAL>(), tables);
-}
-
-template <int NP>
-int qba_launch_mc(qba_ctx *ctx, const QbaMc &M) {
-  return qba_mc_with_program<NP>(ctx, [&](auto s, size_t tables) {
-    return qba_launch_mc_s<NP, decltype(s)::value>(ctx, M, tables);
-  });
-}
-
-// The shape of the shipped programs' kernel (closed form up to n = 11, the
-// canonical tables above): qba_montecarlo_shape
-template <int NP>
-void qba_mc_shape_n(int *waves, int64_t *lds, int *wgs) {
-  constexpr int SAMP = NP <= QBA_CLOSED_MAX_N ? QBA_S_CLOSED : QBA_S_FAST;
-  constexpr QbaMcShape sh = qba_mc_shape(qba_mc_tables<NP, SAMP>(), QCfg<NP>::G, QCfg<NP>::W, 16);
-  *waves = sh.waves;
-  *lds = (int64_t)sh.lds;
-  *wgs = sh.wgs;
-}
-
 // ---------------------------------------------------------------------------
 // qba_montecarlo_curve_sampled: the same instances decided at every checkpoint
 // c_0 < c_1 < ... of one pass over their entries.
@@ -206,12 +138,6 @@ void qba_mc_shape_n(int *waves, int64_t *lds, int *wgs) {
 __host__ __device__ constexpr size_t qba_mc_acc_lds(int G, int w) {
   return (size_t)((mc_acc_words(G, w) + 3) & ~3) * sizeof(uint32_t);
 }
-template <int NP, int SAMP>
-constexpr int qba_mc_curve_waves() {
-  using C = QCfg<NP>;
-  return qba_mc_shape(qba_mc_tables<NP, SAMP>(), C::G, C::W, 16, qba_mc_acc_lds(C::G, C::W)).waves;
-}
-
 template <int NP, int SAMP, int NW>
 __global__ void __attribute__((amdgpu_flat_work_group_size(64, NW * 64)))
     qba_k_mc_curve_sampled(const QbaProgramSet *__restrict__ ps, uint64_t seed_base, int64_t n_inst, int n_dis,
@@ -282,61 +208,124 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64, NW * 64)))
   }
 }
 
-template <int NP, int SAMP>
-static QbaMcShape qba_mc_curve_run_shape(size_t tables) {  // as qba_mc_run_shape
-  using C = QCfg<NP>;
-  return qba_mc_shape(tables, C::G, C::W, qba_mc_curve_waves<NP, SAMP>(), qba_mc_acc_lds(C::G, C::W));
-}
 
-template <int NP, int SAMP>
-static int qba_launch_mc_curve_s(qba_ctx *ctx, const QbaMcCurve &M, size_t tables) {
-  constexpr int NW = qba_mc_curve_waves<NP, SAMP>();
+// The sampled kernel of (NP, SAMP) for one count (qba_k_mc_sampled) or for a
+// curve (qba_k_mc_curve_sampled), as the host sees it; everything below is
+// written once over this.
+template <int NP, int SAMP_, bool CURVE_>
+struct QbaMcKern {
+  using C = QCfg<NP>;
+  static constexpr int SAMP = SAMP_;
+  static constexpr bool CURVE = CURVE_;
+  // LDS of a wave beside its ProtoShared and mailbox
+  static constexpr size_t EXTRA = CURVE ? qba_mc_acc_lds(C::G, C::W) : 0;
+  // waves per workgroup the kernel is compiled for
+  static constexpr int NW = qba_mc_shape(qba_mc_tables<NP, SAMP>(), C::G, C::W, 16, EXTRA).waves;
   static_assert(NW >= 1, "no room for a wave beside the tables");
-  const QbaMcShape sh = qba_mc_curve_run_shape<NP, SAMP>(tables);
+  static const void *kernel() {
+    if constexpr (CURVE)
+      return (const void *)qba_k_mc_curve_sampled<NP, SAMP, NW>;
+    else  // not instantiated for a curve's NW
+      return (const void *)qba_k_mc_sampled<NP, SAMP, NW>;
+  }
+  // The shape a program with `tables` bytes of staged tables runs the kernel
+  // in: at most the compiled wave count (the launcher and both shape queries
+  // ask here).
+  static QbaMcShape run_shape(size_t tables) { return qba_mc_shape(tables, C::G, C::W, NW, EXTRA); }
+};
+
+// The launch of one sampler's kernel: full workgroups of its compiled wave
+// count, of which nw_run work; persistent over the instances.
+template <class K>
+static int qba_launch_mc_s(qba_ctx *ctx, const QbaMc &M, size_t tables) {
+  const QbaMcShape sh = K::run_shape(tables);
   if (sh.waves < 1)
-    return qba_fail(QBA_EUNSUPPORTED, "qba_montecarlo_curve_sampled: the program's tables leave no LDS for a wave");
-  const void *kern = (const void *)qba_k_mc_curve_sampled<NP, SAMP, NW>;
-  if (int rc = lds_allow(kern, sh.lds)) return rc;
+    return qba_fail(QBA_EUNSUPPORTED, std::string(M.who) + ": the program's tables leave no LDS for a wave");
+  if (int rc = lds_allow(K::kernel(), sh.lds)) return rc;
   const int64_t need = (M.n_inst + sh.waves - 1) / sh.waves, cap = (int64_t)ctx->num_cus * sh.wgs;
   const int grid = (int)(need < cap ? need : cap);
   const int nw_run = sh.waves;
-  const void *args[] = {&M.ps, &M.seed_base, &M.n_inst, &M.n_dis, &nw_run, &M.out, &M.counts};
-  QBA_HIP(hipLaunchKernel(kern, dim3(grid), dim3(NW * 64), const_cast<void **>(args), sh.lds, M.stream));
+  // qba_k_mc_sampled takes the one count where qba_k_mc_curve_sampled takes them all, last
+  const void *one[] = {&M.ps, &M.seed_base, &M.n_inst, &M.counts.c[0], &M.n_dis, &nw_run, &M.out};
+  const void *all[] = {&M.ps, &M.seed_base, &M.n_inst, &M.n_dis, &nw_run, &M.out, &M.counts};
+  QBA_HIP(hipLaunchKernel(K::kernel(), dim3(grid), dim3(K::NW * 64), const_cast<void **>(K::CURVE ? all : one), sh.lds,
+                          M.stream));
   QBA_HIP(hipGetLastError());
   return QBA_OK;
 }
 
-template <int NP>
-int qba_launch_mc_curve(qba_ctx *ctx, const QbaMcCurve &M) {
-  return qba_mc_with_program<NP>(ctx, [&](auto s, size_t tables) {
-    return qba_launch_mc_curve_s<NP, decltype(s)::value>(ctx, M, tables);
+// f(std::integral_constant<int, SAMP>(), tables) for the program compiled for
+// NP: its sampler, as qba_launch_batched chooses it, and the bytes of its
+// staged tables.
+template <int NP, class F>
+static int qba_mc_with_program(qba_ctx *ctx, const F &f) {
+  const QbaProgramSet *hs = reinterpret_cast<const QbaProgramSet *>(ctx->prog_host[NP]);
+  const int samp = sampler_of<NP>(hs);
+  if (int rc = check_closed<NP>(hs)) return rc;
+  const size_t tables = table_lds<NP>(hs, samp);
+  if (samp == QBA_S_CLOSED) {
+    if constexpr (NP <= QBA_CLOSED_MAX_N) return f(std::integral_constant<int, QBA_S_CLOSED>(), tables);
+    return qba_fail(QBA_EUNSUPPORTED, "closed form beyond n = 11");
+  }
+  if (samp == QBA_S_FAST) return f(std::integral_constant<int, QBA_S_FAST>(), tables);
+  return f(std::integral_constant<int, QBA_S_GENERAL>(), tables);
+}
+
+// f(std::bool_constant<curve>()).  The single-count branch stands first, and
+// callers choose the sampler inside f: the compiler then instantiates, and lays
+// out in the code object, the three single-count kernels before the curve
+// kernels, the order tools/codeobj_diff.py finds them in since both exist.
+template <class F>
+static int qba_mc_with_curve(bool curve, const F &f) {
+  if (!curve) return f(std::false_type());
+  return f(std::true_type());
+}
+
+// f(QbaMcKern of the program compiled for NP, tables)
+template <int NP, class F>
+static int qba_mc_with_kern(qba_ctx *ctx, bool curve, const F &f) {
+  return qba_mc_with_curve(curve, [&](auto c) {
+    return qba_mc_with_program<NP>(ctx, [&](auto s, size_t tables) {
+      return f(QbaMcKern<NP, decltype(s)::value, decltype(c)::value>(), tables);
+    });
   });
 }
 
-// qba_montecarlo_program_shape: what the two launchers above would run the
-// program compiled for NP in, from the same sampler choice, table bytes and
-// shape functions; launches nothing.
 template <int NP>
-int qba_mc_program_shape_n(qba_ctx *ctx, int curve, int *sampler, int *waves_compiled, int *waves_run, int64_t *lds,
-                           int *wgs) {
-  return qba_mc_with_program<NP>(ctx, [&](auto s, size_t tables) {
-    constexpr int SAMP = decltype(s)::value;
-    const QbaMcShape sh = curve ? qba_mc_curve_run_shape<NP, SAMP>(tables) : qba_mc_run_shape<NP, SAMP>(tables);
-    *sampler = SAMP;
-    *waves_compiled = curve ? qba_mc_curve_waves<NP, SAMP>() : qba_mc_waves<NP, SAMP>();
-    *waves_run = sh.waves;
-    *lds = (int64_t)sh.lds;
-    *wgs = sh.wgs;
-    return (int)QBA_OK;
+int qba_launch_mc(qba_ctx *ctx, const QbaMc &M) {
+  return qba_mc_with_kern<NP>(ctx, M.curve, [&](auto k, size_t tables) {
+    return qba_launch_mc_s<decltype(k)>(ctx, M, tables);
   });
 }
 
-template <int NP>
-void qba_mc_curve_shape_n(int *waves, int64_t *lds, int *wgs) {
-  using C = QCfg<NP>;
-  constexpr int SAMP = NP <= QBA_CLOSED_MAX_N ? QBA_S_CLOSED : QBA_S_FAST;
-  constexpr QbaMcShape sh = qba_mc_shape(qba_mc_tables<NP, SAMP>(), C::G, C::W, 16, qba_mc_acc_lds(C::G, C::W));
+static int qba_mc_put_shape(const QbaMcShape &sh, int *waves, int64_t *lds, int *wgs) {
   *waves = sh.waves;
   *lds = (int64_t)sh.lds;
   *wgs = sh.wgs;
+  return QBA_OK;
+}
+
+// qba_montecarlo_shape / _curve_shape: the shape of the shipped programs'
+// kernel (closed form up to n = 11, else the canonical tables of qba_mc_tables)
+template <int NP>
+void qba_mc_shape_n(int curve, int *waves, int64_t *lds, int *wgs) {
+  constexpr int SAMP = NP <= QBA_CLOSED_MAX_N ? QBA_S_CLOSED : QBA_S_FAST;
+  qba_mc_with_curve(curve, [&](auto c) {
+    using K = QbaMcKern<NP, SAMP, decltype(c)::value>;
+    return qba_mc_put_shape(K::run_shape(qba_mc_tables<NP, SAMP>()), waves, lds, wgs);
+  });
+}
+
+// qba_montecarlo_program_shape: what qba_launch_mc would run the program
+// compiled for NP in, from the same sampler choice, table bytes and kernel
+// description; launches nothing.
+template <int NP>
+int qba_mc_program_shape_n(qba_ctx *ctx, int curve, int *sampler, int *waves_compiled, int *waves_run, int64_t *lds,
+                           int *wgs) {
+  return qba_mc_with_kern<NP>(ctx, curve, [&](auto k, size_t tables) {
+    using K = decltype(k);
+    *sampler = K::SAMP;
+    *waves_compiled = K::NW;
+    return qba_mc_put_shape(K::run_shape(tables), waves_run, lds, wgs);
+  });
 }

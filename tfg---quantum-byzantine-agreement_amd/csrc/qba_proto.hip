@@ -18,8 +18,6 @@
 //             rows into the same masks (mc_entry, qba_proto_rounds.h)
 #include "qba_proto_rounds.h"
 
-#define QBA_PROTO_LAUNCH (1 << 20)  // instances per launch
-
 namespace {
 
 __global__ __launch_bounds__(QBA_PROTO_BLOCK) void qba_k_protocol(int n, int n_dis, uint64_t seed_base,
@@ -153,6 +151,21 @@ __global__ __launch_bounds__(QBA_PROTO_BLOCK) void qba_k_mc_curve_lists(int n, i
 
 }  // namespace
 
+
+// The launches of a one-wave-per-instance kernel: launch(first, grid) starts
+// instances [first, first + grid.x), at most 2^20 a time.
+template <class F>
+static int launch_chunks(qba_ctx *ctx, int64_t n_inst, const F &launch) {
+  constexpr int64_t QBA_PROTO_LAUNCH = 1 << 20;  // instances per launch
+  if (int rc = qba_set_device(ctx)) return rc;
+  for (int64_t first = 0; first < n_inst; first += QBA_PROTO_LAUNCH) {
+    const int64_t blocks = n_inst - first < QBA_PROTO_LAUNCH ? n_inst - first : QBA_PROTO_LAUNCH;
+    launch(first, dim3((unsigned)blocks));
+    QBA_HIP(hipGetLastError());
+  }
+  return QBA_OK;
+}
+
 extern "C" int qba_protocol_batched(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
                                     const int64_t *H, const int64_t *C, const int64_t *P, int32_t *out,
                                     qba_stream stream) {
@@ -164,92 +177,83 @@ extern "C" int qba_protocol_batched(qba_ctx *ctx, int n, int n_dis, uint64_t see
   if (n_inst < 0) return qba_fail(QBA_EINVAL, "qba_protocol_batched: n_instances < 0");
   if (n_inst == 0) return QBA_OK;
   if (!H || !C || !P || !out) return qba_fail(QBA_EINVAL, "qba_protocol_batched: a table or out pointer is NULL");
-  int rc = qba_set_device(ctx);
-  if (rc) return rc;
   const int G = n + 1, w = 1 << qba_nq(n);
   const size_t lds = (size_t)proto_box_words(G, w) * sizeof(uint32_t);  // <= 32896 B at n = 15
-  for (int64_t first = 0; first < n_inst; first += QBA_PROTO_LAUNCH) {
-    const int64_t blocks = n_inst - first < QBA_PROTO_LAUNCH ? n_inst - first : QBA_PROTO_LAUNCH;
-    hipLaunchKernelGGL(qba_k_protocol, dim3((unsigned)blocks), dim3(QBA_PROTO_BLOCK), lds, (hipStream_t)stream,
-                       n, n_dis, seed_base, first, H, C, P, out);
-    QBA_HIP(hipGetLastError());
-  }
-  return QBA_OK;
+  return launch_chunks(ctx, n_inst, [&](int64_t first, dim3 grid) {
+    hipLaunchKernelGGL(qba_k_protocol, grid, dim3(QBA_PROTO_BLOCK), lds, (hipStream_t)stream, n, n_dis, seed_base,
+                       first, H, C, P, out);
+  });
 }
 
-// The argument envelope of the two fused calls (that of qba_protocol_batched,
-// then count): n_parties, n_dishonest and count are checked before ctx.
-int qba_mc_check(const char *who, qba_ctx *ctx, int n, int n_dis, int64_t n_inst, uint64_t count,
+// The argument envelope of the four Monte-Carlo calls (that of
+// qba_protocol_batched with the count in the middle), in the order of
+// rejection: n_parties, n_dishonest, `bad_count` (what is wrong with the count
+// or the checkpoints; NULL: nothing), then ctx, n_instances and out.
+int qba_mc_check(const char *who, qba_ctx *ctx, int n, int n_dis, const char *bad_count, int64_t n_inst,
                  const void *out) {
   const std::string f(who);
   if (n < 1 || n > QBA_MAX_PARTIES) return qba_fail(QBA_EINVAL, f + ": n_parties must be in [1, 15]");
   if (n_dis < 0 || n_dis > n) return qba_fail(QBA_EINVAL, f + ": n_dishonest must be in [0, n_parties]");
-  if (count >= (1ull << 31)) return qba_fail(QBA_EINVAL, f + ": count must be < 2^31");
+  if (bad_count) return qba_fail(QBA_EINVAL, f + ": " + bad_count);
   if (!ctx) return qba_fail(QBA_EINVAL, f + ": ctx is NULL");
   if (n_inst < 0) return qba_fail(QBA_EINVAL, f + ": n_instances < 0");
   if (n_inst > 0 && !out) return qba_fail(QBA_EINVAL, f + ": out is NULL");
   return QBA_OK;
 }
 
-extern "C" int qba_montecarlo_lists(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
-                                    uint64_t count, const uint8_t *lists, uint64_t ld, uint64_t inst_stride,
-                                    int32_t *out, qba_stream stream) {
-  int rc = qba_mc_check("qba_montecarlo_lists", ctx, n, n_dis, n_inst, count, out);
-  if (rc) return rc;
-  if (count && n_inst && (!lists || ld < count || (n_inst > 1 && inst_stride < (uint64_t)(n + 1) * ld)))
-    return qba_fail(QBA_EINVAL, "qba_montecarlo_lists: need lists, ld >= count and inst_stride >= (n+1)*ld");
-  if (n_inst == 0) return QBA_OK;
-  if ((rc = qba_set_device(ctx))) return rc;
-  const int G = n + 1, w = 1 << qba_nq(n);
-  const size_t lds = (size_t)(PROTO_S_WORDS + proto_box_words(G, w)) * sizeof(uint32_t);  // <= 34960 B
-  for (int64_t first = 0; first < n_inst; first += QBA_PROTO_LAUNCH) {
-    const int64_t blocks = n_inst - first < QBA_PROTO_LAUNCH ? n_inst - first : QBA_PROTO_LAUNCH;
-    hipLaunchKernelGGL(qba_k_mc_lists, dim3((unsigned)blocks), dim3(QBA_PROTO_BLOCK), lds, (hipStream_t)stream, n,
-                       n_dis, seed_base, first, (uint32_t)count, lists, ld, inst_stride, out);
-    QBA_HIP(hipGetLastError());
-  }
-  return QBA_OK;
+static const char *bad_counts(const uint32_t *counts, int n_counts) {
+  if (!counts) return "counts is NULL";
+  if (n_counts < 1 || n_counts > QBA_MC_CURVE_MAX) return "n_counts must be in [1, 32]";
+  for (int j = 1; j < n_counts; ++j)
+    if (counts[j] <= counts[j - 1]) return "counts must be strictly increasing";
+  return counts[n_counts - 1] >= (1u << 31) ? "counts must be < 2^31" : nullptr;
 }
 
 int qba_mc_curve_check(const char *who, qba_ctx *ctx, int n, int n_dis, int64_t n_inst, const uint32_t *counts,
                        int n_counts, const void *out, QbaMcCounts *cv) {
-  const std::string f(who);
-  if (n < 1 || n > QBA_MAX_PARTIES) return qba_fail(QBA_EINVAL, f + ": n_parties must be in [1, 15]");
-  if (n_dis < 0 || n_dis > n) return qba_fail(QBA_EINVAL, f + ": n_dishonest must be in [0, n_parties]");
-  if (!counts) return qba_fail(QBA_EINVAL, f + ": counts is NULL");
-  if (n_counts < 1 || n_counts > QBA_MC_CURVE_MAX) return qba_fail(QBA_EINVAL, f + ": n_counts must be in [1, 32]");
-  for (int j = 1; j < n_counts; ++j)
-    if (counts[j] <= counts[j - 1]) return qba_fail(QBA_EINVAL, f + ": counts must be strictly increasing");
-  if (counts[n_counts - 1] >= (1u << 31)) return qba_fail(QBA_EINVAL, f + ": counts must be < 2^31");
-  if (!ctx) return qba_fail(QBA_EINVAL, f + ": ctx is NULL");
-  if (n_inst < 0) return qba_fail(QBA_EINVAL, f + ": n_instances < 0");
-  if (n_inst > 0 && !out) return qba_fail(QBA_EINVAL, f + ": out is NULL");
+  if (int rc = qba_mc_check(who, ctx, n, n_dis, bad_counts(counts, n_counts), n_inst, out)) return rc;
   *cv = QbaMcCounts{};
   for (int j = 0; j < n_counts; ++j) cv->c[j] = counts[j];
   cv->n = n_counts;
   return QBA_OK;
 }
 
+// The injected rows of the two list calls hold `need` entries (the count, or
+// the last checkpoint) per row without overlapping.
+static int lists_check(const char *who, int n, int64_t n_inst, uint64_t need, const uint8_t *lists, uint64_t ld,
+                       uint64_t inst_stride) {
+  if (need && n_inst && (!lists || ld < need || (n_inst > 1 && inst_stride < (uint64_t)(n + 1) * ld)))
+    return qba_fail(QBA_EINVAL,
+                    std::string(who) + ": need lists, ld >= the (last) count and inst_stride >= (n+1)*ld");
+  return QBA_OK;
+}
+
+extern "C" int qba_montecarlo_lists(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
+                                    uint64_t count, const uint8_t *lists, uint64_t ld, uint64_t inst_stride,
+                                    int32_t *out, qba_stream stream) {
+  const char *who = "qba_montecarlo_lists";
+  int rc = qba_mc_check(who, ctx, n, n_dis, count >> 31 ? "count must be < 2^31" : nullptr, n_inst, out);
+  if (rc || (rc = lists_check(who, n, n_inst, count, lists, ld, inst_stride)) || n_inst == 0) return rc;
+  const int G = n + 1, w = 1 << qba_nq(n);
+  const size_t lds = (size_t)(PROTO_S_WORDS + proto_box_words(G, w)) * sizeof(uint32_t);  // <= 34960 B
+  return launch_chunks(ctx, n_inst, [&](int64_t first, dim3 grid) {
+    hipLaunchKernelGGL(qba_k_mc_lists, grid, dim3(QBA_PROTO_BLOCK), lds, (hipStream_t)stream, n, n_dis, seed_base,
+                       first, (uint32_t)count, lists, ld, inst_stride, out);
+  });
+}
+
 extern "C" int qba_montecarlo_curve_lists(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
                                           const uint32_t *counts, int n_counts, const uint8_t *lists, uint64_t ld,
                                           uint64_t inst_stride, int32_t *out, qba_stream stream) {
+  const char *who = "qba_montecarlo_curve_lists";
   QbaMcCounts cv;
-  int rc = qba_mc_curve_check("qba_montecarlo_curve_lists", ctx, n, n_dis, n_inst, counts, n_counts, out, &cv);
-  if (rc) return rc;
-  const uint64_t cmax = cv.c[cv.n - 1];
-  if (cmax && n_inst && (!lists || ld < cmax || (n_inst > 1 && inst_stride < (uint64_t)(n + 1) * ld)))
-    return qba_fail(QBA_EINVAL,
-                    "qba_montecarlo_curve_lists: need lists, ld >= the last count and inst_stride >= (n+1)*ld");
-  if (n_inst == 0) return QBA_OK;
-  if ((rc = qba_set_device(ctx))) return rc;
+  int rc = qba_mc_curve_check(who, ctx, n, n_dis, n_inst, counts, n_counts, out, &cv);
+  if (rc || (rc = lists_check(who, n, n_inst, cv.c[cv.n - 1], lists, ld, inst_stride)) || n_inst == 0) return rc;
   const int G = n + 1, w = 1 << qba_nq(n);
   const size_t lds = (size_t)(PROTO_S_WORDS + ((proto_box_words(G, w) + 3) & ~3) + mc_acc_words(G, w)) *
                      sizeof(uint32_t);  // <= 37024 B
-  for (int64_t first = 0; first < n_inst; first += QBA_PROTO_LAUNCH) {
-    const int64_t blocks = n_inst - first < QBA_PROTO_LAUNCH ? n_inst - first : QBA_PROTO_LAUNCH;
-    hipLaunchKernelGGL(qba_k_mc_curve_lists, dim3((unsigned)blocks), dim3(QBA_PROTO_BLOCK), lds, (hipStream_t)stream,
-                       n, n_dis, seed_base, first, n_inst, lists, ld, inst_stride, out, cv);
-    QBA_HIP(hipGetLastError());
-  }
-  return QBA_OK;
+  return launch_chunks(ctx, n_inst, [&](int64_t first, dim3 grid) {
+    hipLaunchKernelGGL(qba_k_mc_curve_lists, grid, dim3(QBA_PROTO_BLOCK), lds, (hipStream_t)stream, n, n_dis,
+                       seed_base, first, n_inst, lists, ld, inst_stride, out, cv);
+  });
 }

@@ -26,6 +26,11 @@ def _i32p(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+def _u64(x) -> int:
+    """A seed or an instance index as the uint64 the library takes (mod 2^64)."""
+    return int(x) & ((1 << 64) - 1)
+
+
 @dataclass
 class Counts:
     """Count-mode result of one pass (see qba.h): int64 device tensors."""
@@ -269,76 +274,28 @@ class Engine:
             if t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous() or \
                     t.device != self.device:
                 raise QbaError("counts must be contiguous int64 [n_inst, ...] tensors of sample_check_batched")
-        words = 4 + 5 * g
-        if out is None:
-            out = torch.empty((n_inst, words), dtype=torch.int32, device=self.device)
-        if out.dtype != torch.int32 or tuple(out.shape) != (n_inst, words) or not out.is_contiguous() or \
-                out.device != self.device:
-            raise QbaError(f"out must be a contiguous int32 [{n_inst}, {words}] device tensor")
+        out = self._rows_out(n, n_inst, out)
         call("qba_protocol_batched", self.ctx, n, n_dishonest, seed_base, n_inst, _ptr(counts.H), _ptr(counts.C),
              _ptr(counts.P), _ptr(out), self.stream())
         return out
 
-    def _rows_out(self, n: int, n_inst: int, out: Optional[torch.Tensor]) -> torch.Tensor:
-        words = 4 + 5 * (n + 1)
+    def _rows_out(self, n: int, n_inst: int, out: Optional[torch.Tensor], k: Optional[int] = None) -> torch.Tensor:
+        """``out``, or a new buffer when it is None: result rows [n_inst, words],
+        or [k, n_inst, words] of a curve call."""
+        shape = (n_inst, 4 + 5 * (n + 1)) if k is None else (k, n_inst, 4 + 5 * (n + 1))
         if out is None:
-            out = torch.empty((n_inst, words), dtype=torch.int32, device=self.device)
-        if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != (n_inst, words) or \
+            out = torch.empty(shape, dtype=torch.int32, device=self.device)
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != shape or \
                 not out.is_contiguous() or out.device != self.device:
-            raise QbaError(f"out must be a contiguous int32 [{n_inst}, {words}] device tensor")
+            raise QbaError(f"out must be a contiguous int32 {list(shape)} device tensor")
         return out
 
-    @staticmethod
-    def _check_mc(n: int, n_dishonest: int, n_inst: int, count: int) -> None:
-        if not 0 <= n_dishonest <= n:
-            raise QbaError(f"n_dishonest={n_dishonest} outside [0, {n}]")
-        if n_inst < 0 or not 0 <= count < 1 << 31:
-            raise QbaError("n_inst >= 0 and 0 <= count < 2^31")
-
-    def montecarlo_sampled(self, n: int, n_dishonest: int, seed_base: int, n_inst: int, count: int,
-                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """n_inst instances (key seed_base + i) of `count` entries sampled,
-        distilled and decided in one kernel (qba_montecarlo_sampled): the rows
-        of protocol_batched(sample_check_batched(...)), int32
-        [n_inst, 4 + 5*(n+1)], with no list buffer and no count tables."""
-        self._check_n(n)
-        self._check_mc(n, n_dishonest, n_inst, count)
-        self.prepare(n)
-        out = self._rows_out(n, n_inst, out)
-        call("qba_montecarlo_sampled", self.ctx, n, n_dishonest, int(seed_base) & ((1 << 64) - 1), n_inst, count,
-             _ptr(out), self.stream())
-        return out
-
-    def montecarlo_lists(self, n: int, n_dishonest: int, seed_base: int, lists, count: int,
-                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The same rows from injected lists (qba_montecarlo_lists): a uint8
-        [n_inst, n+1, >= count] device tensor in the layout of
-        sample_check_batched, or a host array of that shape (copied to the
-        device).  A row's status 4 marks a value >= w at a Q-correlated
-        position (montecarlo.ST_RANGE)."""
-        self._check_n(n)
-        if isinstance(lists, np.ndarray):
-            lists = torch.from_numpy(np.array(lists, dtype=np.uint8, order="C")).to(self.device)  # a writable copy
-        if not isinstance(lists, torch.Tensor) or lists.dtype != torch.uint8 or lists.dim() != 3 or \
-                lists.shape[1] != n + 1 or lists.device != self.device or \
-                (lists.numel() and lists.stride(2) != 1) or lists.shape[2] < count:
-            raise QbaError("lists must be a uint8 [n_inst, n+1, >= count] device tensor with unit column stride")
-        n_inst = lists.shape[0]
-        self._check_mc(n, n_dishonest, n_inst, count)
-        ld, stride = (lists.stride(1), lists.stride(0)) if lists.numel() else (count, (n + 1) * count)
-        if count and n_inst and (ld < count or (n_inst > 1 and stride < (n + 1) * ld)):
-            raise QbaError("lists rows overlap: need stride(1) >= count and stride(0) >= (n+1)*stride(1)")
-        out = self._rows_out(n, n_inst, out)
-        call("qba_montecarlo_lists", self.ctx, n, n_dishonest, int(seed_base) & ((1 << 64) - 1), n_inst, count,
-             _ptr(lists), ld, stride, _ptr(out), self.stream())
-        return out
-
-    # -- a whole sizeL curve in one pass (qba_montecarlo_curve_*) ------------------
     CURVE_MAX = 32  # QBA_MC_CURVE_MAX
 
     @classmethod
     def _check_curve(cls, n: int, n_dishonest: int, n_inst: int, counts) -> list:
-        """The checkpoints as a list of ints; validation as _check_mc."""
+        """The argument check of the four montecarlo_* methods; returns the
+        checkpoints as a list of ints.  A single-count call is ``[count]``."""
         try:
             cs = [int(c) for c in counts]
         except TypeError:
@@ -353,15 +310,52 @@ class Engine:
             raise QbaError("n_inst >= 0")
         return cs
 
-    def _curve_out(self, n: int, k: int, n_inst: int, out: Optional[torch.Tensor]) -> torch.Tensor:
-        shape = (k, n_inst, 4 + 5 * (n + 1))
-        if out is None:
-            out = torch.empty(shape, dtype=torch.int32, device=self.device)
-        if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != shape or \
-                not out.is_contiguous() or out.device != self.device:
-            raise QbaError(f"out must be a contiguous int32 {list(shape)} device tensor")
+    def _mc_lists(self, n: int, lists, need: int):
+        """Injected lists, a uint8 [n_inst, n+1, >= need] device tensor or a
+        host array of that shape (copied to the device), as ``(lists, n_inst,
+        ld, inst_stride)``."""
+        if isinstance(lists, np.ndarray):
+            lists = torch.from_numpy(np.array(lists, dtype=np.uint8, order="C")).to(self.device)  # a writable copy
+        if not isinstance(lists, torch.Tensor) or lists.dtype != torch.uint8 or lists.dim() != 3 or \
+                lists.shape[1] != n + 1 or lists.device != self.device or \
+                (lists.numel() and lists.stride(2) != 1) or lists.shape[2] < need:
+            raise QbaError(f"lists must be a uint8 [n_inst, n+1, >= {need}] device tensor with unit column stride")
+        n_inst = lists.shape[0]
+        ld, stride = (lists.stride(1), lists.stride(0)) if lists.numel() else (need, (n + 1) * need)
+        if need and n_inst and (ld < need or (n_inst > 1 and stride < (n + 1) * ld)):
+            raise QbaError(f"lists rows overlap: need stride(1) >= {need} and stride(0) >= (n+1)*stride(1)")
+        return lists, n_inst, ld, stride
+
+    def montecarlo_sampled(self, n: int, n_dishonest: int, seed_base: int, n_inst: int, count: int,
+                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """n_inst instances (key seed_base + i) of `count` entries sampled,
+        distilled and decided in one kernel (qba_montecarlo_sampled): the rows
+        of protocol_batched(sample_check_batched(...)), int32
+        [n_inst, 4 + 5*(n+1)], with no list buffer and no count tables."""
+        self._check_n(n)
+        self._check_curve(n, n_dishonest, n_inst, [count])
+        self.prepare(n)
+        out = self._rows_out(n, n_inst, out)
+        call("qba_montecarlo_sampled", self.ctx, n, n_dishonest, _u64(seed_base), n_inst, count, _ptr(out),
+             self.stream())
         return out
 
+    def montecarlo_lists(self, n: int, n_dishonest: int, seed_base: int, lists, count: int,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The same rows from injected lists (qba_montecarlo_lists): a uint8
+        [n_inst, n+1, >= count] device tensor in the layout of
+        sample_check_batched, or a host array of that shape (copied to the
+        device).  A row's status 4 marks a value >= w at a Q-correlated
+        position (montecarlo.ST_RANGE)."""
+        self._check_n(n)
+        self._check_curve(n, n_dishonest, 0, [count])
+        lists, n_inst, ld, stride = self._mc_lists(n, lists, count)
+        out = self._rows_out(n, n_inst, out)
+        call("qba_montecarlo_lists", self.ctx, n, n_dishonest, _u64(seed_base), n_inst, count, _ptr(lists), ld, stride,
+             _ptr(out), self.stream())
+        return out
+
+    # -- a whole sizeL curve in one pass (qba_montecarlo_curve_*) ------------------
     def montecarlo_curve_sampled(self, n: int, n_dishonest: int, seed_base: int, n_inst: int, counts,
                                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The n_inst instances of montecarlo_sampled decided at every count of
@@ -371,10 +365,9 @@ class Engine:
         self._check_n(n)
         cs = self._check_curve(n, n_dishonest, n_inst, counts)
         self.prepare(n)
-        out = self._curve_out(n, len(cs), n_inst, out)
-        arr = (C.c_uint32 * len(cs))(*cs)
-        call("qba_montecarlo_curve_sampled", self.ctx, n, n_dishonest, int(seed_base) & ((1 << 64) - 1), n_inst, arr,
-             len(cs), _ptr(out), self.stream())
+        out = self._rows_out(n, n_inst, out, len(cs))
+        call("qba_montecarlo_curve_sampled", self.ctx, n, n_dishonest, _u64(seed_base), n_inst,
+             (C.c_uint32 * len(cs))(*cs), len(cs), _ptr(out), self.stream())
         return out
 
     def montecarlo_curve_lists(self, n: int, n_dishonest: int, seed_base: int, lists, counts,
@@ -384,23 +377,11 @@ class Engine:
         montecarlo_lists(count=counts[j]).  A value >= w at Q-correlated
         position k gives status 4 in exactly the slices with counts[j] > k."""
         self._check_n(n)
-        if isinstance(lists, np.ndarray):
-            lists = torch.from_numpy(np.array(lists, dtype=np.uint8, order="C")).to(self.device)  # a writable copy
-        if not isinstance(lists, torch.Tensor) or lists.dtype != torch.uint8 or lists.dim() != 3 or \
-                lists.shape[1] != n + 1 or lists.device != self.device or (lists.numel() and lists.stride(2) != 1):
-            raise QbaError("lists must be a uint8 [n_inst, n+1, >= counts[-1]] device tensor with unit column stride")
-        n_inst = lists.shape[0]
-        cs = self._check_curve(n, n_dishonest, n_inst, counts)
-        cmax = cs[-1]
-        if lists.shape[2] < cmax:
-            raise QbaError("lists must be a uint8 [n_inst, n+1, >= counts[-1]] device tensor with unit column stride")
-        ld, stride = (lists.stride(1), lists.stride(0)) if lists.numel() else (cmax, (n + 1) * cmax)
-        if cmax and n_inst and (ld < cmax or (n_inst > 1 and stride < (n + 1) * ld)):
-            raise QbaError("lists rows overlap: need stride(1) >= counts[-1] and stride(0) >= (n+1)*stride(1)")
-        out = self._curve_out(n, len(cs), n_inst, out)
-        arr = (C.c_uint32 * len(cs))(*cs)
-        call("qba_montecarlo_curve_lists", self.ctx, n, n_dishonest, int(seed_base) & ((1 << 64) - 1), n_inst, arr,
-             len(cs), _ptr(lists), ld, stride, _ptr(out), self.stream())
+        cs = self._check_curve(n, n_dishonest, 0, counts)
+        lists, n_inst, ld, stride = self._mc_lists(n, lists, cs[-1])
+        out = self._rows_out(n, n_inst, out, len(cs))
+        call("qba_montecarlo_curve_lists", self.ctx, n, n_dishonest, _u64(seed_base), n_inst,
+             (C.c_uint32 * len(cs))(*cs), len(cs), _ptr(lists), ld, stride, _ptr(out), self.stream())
         return out
 
     @classmethod
@@ -460,7 +441,7 @@ class Engine:
                     capture.shape[0] != k or not capture.is_contiguous() or capture.device != self.device:
                 raise QbaError(f"capture must be a contiguous int64 [{k}, cap] device tensor")
             cap = capture.shape[1]
-        call("qba_montecarlo_tally", self.ctx, n, _ptr(rows), n_inst, k, int(inst_base) & ((1 << 64) - 1), _ptr(tally),
+        call("qba_montecarlo_tally", self.ctx, n, _ptr(rows), n_inst, k, _u64(inst_base), _ptr(tally),
              int(select), _ptr(capture) if cap else None, cap, self.stream())
         return tally
 

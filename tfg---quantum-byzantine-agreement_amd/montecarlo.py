@@ -265,25 +265,38 @@ def summary_from_tally(n: int, tally_row) -> dict:
             "sent": t[T_SENT]}
 
 
-def _tallied(n: int, k: int, runs: int, batch: int, failures: int, engine, decide) -> list:
-    """The summaries of ``k`` slices with the rows tallied on the device:
-    ``decide(off, b, out)`` writes the rows of instances [off, off + b) into
-    ``out`` ([k, b, words], or [b, words] when k == 1); one row buffer of
-    ``batch`` instances serves every batch, and only the [k, 32] tally (and the
-    [k, failures] captured indices) come to the host."""
+def _batches(n: int, k: int, runs: int, batch: int, seed: int, engine, decide, tally: bool, failures: int) -> list:
+    """The summaries of the ``k`` slices of ``runs`` instances decided ``batch``
+    at a time, the batch at offset ``off`` under key ``seed + off``:
+    ``decide(key, b)`` returns the rows of the b instances from ``key`` on,
+    [k, b, words] (or [b, words] when k == 1); ``decide(key, b, out=buffer)``
+    writes them to ``buffer``, always [k, b, words].
+
+    Without ``tally`` and ``failures`` the batches' rows (each call's own
+    buffer) are joined on the host and go through :func:`summarize`.  Otherwise
+    they are tallied on the device: one row buffer of ``batch`` instances
+    serves every batch, and only the [k, 32] tally (and the [k, failures]
+    captured indices) come to the host, for :func:`summary_from_tally`."""
     import torch
+    if runs < 0 or batch < 1:
+        raise ValueError("runs >= 0 and batch >= 1")
+    words = out_words(n)
+    steps = [(off, min(batch, runs - off), (int(seed) + off) & MASK64) for off in range(0, runs, batch)]
+    if not (tally or failures):
+        outs = [decide(key, b).view(k, b, words) for _, b, key in steps]
+        rows = torch.cat(outs, dim=1).cpu().numpy() if outs else np.zeros((k, 0, words), np.int32)
+        return [summarize(n, r) for r in rows]
     if failures < 0:
         raise ValueError("failures >= 0")
     dev = engine.device
-    tally = torch.zeros((k, TALLY_WORDS), dtype=torch.int64, device=dev)
+    tal = torch.zeros((k, TALLY_WORDS), dtype=torch.int64, device=dev)
     capture = torch.zeros((k, failures), dtype=torch.int64, device=dev) if failures else None
-    buf = torch.empty((k, min(batch, runs), out_words(n)), dtype=torch.int32, device=dev) if runs else None
-    for off in range(0, runs, batch):
-        b = min(batch, runs - off)
-        out = buf if b == buf.shape[1] else buf.view(-1)[:k * b * out_words(n)].view(k, b, out_words(n))
-        decide(off, b, out)
-        engine.montecarlo_tally(n, out, tally, inst_base=off, select=SEL_FAILED if failures else 0, capture=capture)
-    host = tally.cpu().numpy()
+    buf = torch.empty(k * min(batch, runs) * words, dtype=torch.int32, device=dev)
+    for off, b, key in steps:
+        out = buf[:k * b * words].view(k, b, words)
+        decide(key, b, out=out)
+        engine.montecarlo_tally(n, out, tal, inst_base=off, select=SEL_FAILED if failures else 0, capture=capture)
+    host = tal.cpu().numpy()
     res = [summary_from_tally(n, row) for row in host]
     if failures:
         cap = capture.cpu().numpy()
@@ -375,39 +388,21 @@ def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, pack
     not grow with ``runs``.  ``failures=F`` adds ``failed_runs``, the sorted
     indices of up to F runs without success (run i has key ``seed + i``), and
     ``failed_total``, how many there were."""
-    import torch
-    if runs < 0 or batch < 1:
-        raise ValueError("runs >= 0 and batch >= 1")
     if path not in ("tables", "fused"):
         raise ValueError("path is 'tables' or 'fused'")
-    if tally or failures:
-        state = {"lists": None}
+    lists = None
 
-        def decide(off, b, out):
-            key = (int(seed) + off) & MASK64
-            if path == "fused":
-                engine.montecarlo_sampled(n, n_dishonest, key, b, sizeL, out=out[0])
-                return
-            li = state["lists"]
-            buf, counts = engine.sample_check_batched(n, key, b, sizeL, None if li is None else li[:b], packed=packed)
-            if li is None:
-                state["lists"] = buf
-            engine.protocol_batched(n, n_dishonest, key, counts, out=out[0])
-        return _tallied(n, 1, runs, batch, failures, engine, decide)[0]
-    lists, outs = None, []
-    for off in range(0, runs, batch):
-        b = min(batch, runs - off)
-        key = (int(seed) + off) & MASK64
+    def decide(key, b, out=None):
+        nonlocal lists
+        into = {} if out is None else {"out": out[0]}
         if path == "fused":
-            outs.append(engine.montecarlo_sampled(n, n_dishonest, key, b, sizeL))
-            continue
+            return engine.montecarlo_sampled(n, n_dishonest, key, b, sizeL, **into)
         buf, counts = engine.sample_check_batched(n, key, b, sizeL, None if lists is None else lists[:b],
                                                   packed=packed)
         if lists is None:
             lists = buf
-        outs.append(engine.protocol_batched(n, n_dishonest, key, counts))
-    rows = torch.cat(outs).cpu().numpy() if outs else np.zeros((0, out_words(n)), np.int32)
-    return summarize(n, rows)
+        return engine.protocol_batched(n, n_dishonest, key, counts, **into)
+    return _batches(n, 1, runs, batch, seed, engine, decide, tally, failures)[0]
 
 
 def curve_host(n: int, counts, n_dishonest: int, n_inst: int, seed_base: int, engine, lists=None) -> np.ndarray:
@@ -430,18 +425,10 @@ def curve(n: int, counts, n_dishonest: int, runs: int, seed: int, engine, batch:
     Returns ``{sizeL: summarize(...)}`` in checkpoint order; the summary at
     sizeL = c is that of ``run(n, c, ..., path="fused")``.  ``tally`` and
     ``failures`` as in :func:`run`, per checkpoint."""
-    import torch
-    if runs < 0 or batch < 1:
-        raise ValueError("runs >= 0 and batch >= 1")
     counts = [int(c) for c in counts]
     if tally or failures:
-        def decide(off, b, out):
-            engine.montecarlo_curve_sampled(n, n_dishonest, (int(seed) + off) & MASK64, b, counts, out=out)
-        engine._check_curve(n, n_dishonest, runs, counts)
-        return dict(zip(counts, _tallied(n, len(counts), runs, batch, failures, engine, decide)))
-    outs = []
-    for off in range(0, runs, batch):
-        b = min(batch, runs - off)
-        outs.append(engine.montecarlo_curve_sampled(n, n_dishonest, (int(seed) + off) & MASK64, b, counts))
-    rows = torch.cat(outs, dim=1).cpu().numpy() if outs else np.zeros((len(counts), 0, out_words(n)), np.int32)
-    return {c: summarize(n, rows[j]) for j, c in enumerate(counts)}
+        engine._check_curve(n, n_dishonest, 0, counts)  # before any device buffer: an empty list has no slice
+
+    def decide(key, b, **into):
+        return engine.montecarlo_curve_sampled(n, n_dishonest, key, b, counts, **into)
+    return dict(zip(counts, _batches(n, len(counts), runs, batch, seed, engine, decide, tally, failures)))
