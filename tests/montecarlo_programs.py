@@ -31,7 +31,9 @@ the GPU tests assert it through Engine.montecarlo_program_shape, never from
 here.  The compiled programs (what Engine.compile returns: the C twin samples
 from them) are kept in tests/golden/montecarlo_programs.npz, written by
 tests/golden/gen_montecarlo_programs.py on a GPU, so that the CPU tests have
-them; the GPU tests hold the compiler to the file.
+them; the GPU tests hold the compiler to the file, and
+tests/test_stabilizer_oracle.py holds the file to the tableau distribution of
+each circuit (oracle/stabilizer.py), which shares nothing with the compiler.
 """
 from pathlib import Path
 

@@ -147,6 +147,39 @@ static void check_circuits(std::mt19937_64 &rng) {
   QbaHostProgram hp;
   CHECK(qba_plan_program(3, facs, hp) == QBA_OK, "non-uniform program");
   CHECK(hp.p.any_nonuniform == 1 && hp.p.fac[0].u_word >= 0 && hp.p.table_len == 4, "non-uniform layout");
+  // Merged factors combine by XOR, as the sampler combines unmerged ones.  The
+  // registers of a circuit touch disjoint bits, where XOR and OR agree, so only
+  // overlapping patterns tell them apart.
+  std::vector<HostFactor> lap(2);
+  lap[0].pat = {0, 3};
+  lap[1].pat = {0, 1};
+  lap[0].prob = lap[1].prob = {0.5, 0.5};
+  CHECK(qba_plan_program(3, lap, hp) == QBA_OK && hp.p.nfac == 1 && hp.p.fac[0].bits == 2 && hp.p.fac[0].uniform,
+        "merge of two factors");
+  std::vector<uint64_t> got(hp.pat);
+  std::sort(got.begin(), got.end());
+  CHECK(got == std::vector<uint64_t>({0, 1, 2, 3}), "merged patterns are not the XORs");
+  // QBA_MAX_FACTORS factors that do not merge (32 * 32 > 256) are a program, one
+  // more is refused.  No circuit gets here: two unmerged neighbours carry >= 9
+  // bits, so 16 factors would need 72 of the at most 64 qubits.
+  for (int nf : {QBA_MAX_FACTORS, QBA_MAX_FACTORS + 1}) {
+    std::vector<HostFactor> many(nf);
+    for (int f = 0; f < nf; ++f)
+      for (int i = 0; i < 32; ++i) {
+        many[f].pat.push_back((uint64_t)(32 * f + i));
+        many[f].prob.push_back(1.0 / 32);
+      }
+    const int rc = qba_plan_program(15, many, hp);
+    if (nf <= QBA_MAX_FACTORS) {
+      CHECK(rc == QBA_OK && hp.p.nfac == nf && hp.p.table_len == 32 * nf && !hp.p.any_nonuniform, "16 factors");
+      for (int f = 0; f < nf && rc == QBA_OK; ++f)  // six 5-bit fields to a 32-bit word
+        CHECK(hp.p.fac[f].bits == 5 && hp.p.fac[f].col_word == f / 6 && hp.p.fac[f].col_shift == 5 * (f % 6) &&
+                  hp.p.fac[f].offset == 32 * f, "factor %d of 16", f);
+    } else {
+      CHECK(rc == QBA_EUNSUPPORTED, "17 factors accepted (%d)", rc);
+      CHECK(std::string(qba_last_error()).find("more than 16 alias tables") != std::string::npos, "17 factors: message");
+    }
+  }
 }
 
 static void check_perm_tables() {
