@@ -52,7 +52,8 @@ def _descriptors(elf: bytes) -> dict:
             group, private, kernarg = struct.unpack_from("<III", kd, 0)
             rsrc1 = struct.unpack_from("<I", kd, 48)[0]
             out[name[:-3]] = {"lds": group, "scratch": private, "kernarg": kernarg,
-                              "vgprs": ((rsrc1 & 0x3F) + 1) * 8}  # gfx950, wave64: granules of 8
+                              "vgprs": ((rsrc1 & 0x3F) + 1) * 8,  # gfx950, wave64: granules of 8
+                              "sgprs": (((rsrc1 >> 6) & 0xF) // 2 + 1) * 16}  # gfx9: granules of 16, field = 2 * (g - 1)
     return out
 
 
@@ -77,7 +78,7 @@ def code_objects(lib: Path):
 
 
 def kernel_descriptors(lib: Path) -> dict:
-    """{mangled kernel name: {"lds", "scratch", "kernarg", "vgprs"}} over
+    """{mangled kernel name: {"lds", "scratch", "kernarg", "vgprs", "sgprs"}} over
     every gfx950 code object in `lib`."""
     out = {}
     for elf in code_objects(lib):

@@ -39,12 +39,13 @@ __global__ void __launch_bounds__(QBA_CT_THREADS)
   }
 }
 
+// The scans are in qba_compact.hip.
 // exclusive scan of ntiles int32 counts -> int64 offsets, total in *total
 __global__ void __launch_bounds__(1024)
     qba_k_compact_scan(const int32_t *__restrict__ counts, int64_t ntiles,
                        int64_t *__restrict__ offsets, int64_t *__restrict__ total);
 
-// multi-block scan of large tile-count arrays (qba_exact.hip)
+// multi-block scan of large tile-count arrays
 #define QBA_SC_T 1024
 #define QBA_SC_PER 8
 #define QBA_SC_CH (QBA_SC_T * QBA_SC_PER)
@@ -54,28 +55,21 @@ __global__ void __launch_bounds__(QBA_SC_T)
     qba_k_scan_apply(const int32_t *__restrict__ counts, int64_t ntiles, const int64_t *__restrict__ boff,
                      int64_t *__restrict__ offsets);
 
-template <class Pred>
-__global__ void __launch_bounds__(QBA_CT_THREADS)
-    qba_k_compact_emit(Pred p, int64_t n, const int64_t *__restrict__ offsets, int64_t cap) {
-  __shared__ int32_t wsum[QBA_CT_THREADS / 64];
-  __shared__ uint32_t flags[QBA_CT_TILE / 4];  // one byte per item of the tile
-  const int64_t tile = blockIdx.x;
-  const int64_t tbase = tile * QBA_CT_TILE;
-  uint8_t *f8 = reinterpret_cast<uint8_t *>(flags);
-#pragma unroll
-  for (int r = 0; r < QBA_CT_ITEMS; ++r) {
-    const int64_t i = tbase + r * QBA_CT_THREADS + threadIdx.x;
-    f8[r * QBA_CT_THREADS + threadIdx.x] = (i < n && p.test(i)) ? 1 : 0;
-  }
+// The rank step of a workgroup of T threads whose T * QBA_CT_ITEMS flag bytes
+// (0 / 1, one per item) are in `flags`: waits for the flags, packs this
+// thread's 16 consecutive items (4 flag words, 0/1 bytes -> 4 bits each)
+// into `bits`, scans the popcounts inclusively over the wave and adds the
+// earlier waves' totals.  Returns the rank of the thread's first item in the
+// workgroup and its item count in c.
+template <int T>
+__device__ __forceinline__ int32_t qba_ct_rank(const uint32_t *flags, uint32_t &bits, int32_t &c) {
+  __shared__ int32_t wsum[T / 64];
   __syncthreads();
-  // this thread's 16 consecutive items: 4 flag words, 0/1 bytes -> 4 bits each
-  const int64_t base = tbase + (int64_t)threadIdx.x * QBA_CT_ITEMS;
-  uint32_t bits = 0;
+  bits = 0;
 #pragma unroll
   for (int q = 0; q < QBA_CT_ITEMS / 4; ++q)
     bits |= ((flags[threadIdx.x * (QBA_CT_ITEMS / 4) + q] * 0x01020408u) >> 24) << (4 * q);
-  const int32_t c = __popc(bits);
-  // inclusive scan over the wave
+  c = __popc(bits);
   int32_t incl = c;
   const int lane = threadIdx.x & 63;
   for (int off = 1; off < 64; off <<= 1) {
@@ -86,13 +80,36 @@ __global__ void __launch_bounds__(QBA_CT_THREADS)
   __syncthreads();
   int32_t wbase = 0;
   for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) wbase += wsum[w];
-  int64_t pos = offsets[tile] + wbase + incl - c;
+  return wbase + incl - c;
+}
+
+// emits the items set in `bits` (bit k: item base + k) at ranks pos, pos + 1, ... below cap
+template <class Pred>
+__device__ __forceinline__ void qba_ct_emit(const Pred &p, uint32_t bits, int64_t base, int64_t pos, int64_t cap) {
   while (bits) {
     const int k = __ffs(bits) - 1;
     bits &= bits - 1;
     if (pos < cap) p.emit(base + k, pos);
     ++pos;
   }
+}
+
+template <class Pred>
+__global__ void __launch_bounds__(QBA_CT_THREADS)
+    qba_k_compact_emit(Pred p, int64_t n, const int64_t *__restrict__ offsets, int64_t cap) {
+  __shared__ uint32_t flags[QBA_CT_TILE / 4];  // one byte per item of the tile
+  const int64_t tile = blockIdx.x;
+  const int64_t tbase = tile * QBA_CT_TILE;
+  uint8_t *f8 = reinterpret_cast<uint8_t *>(flags);
+#pragma unroll
+  for (int r = 0; r < QBA_CT_ITEMS; ++r) {
+    const int64_t i = tbase + r * QBA_CT_THREADS + threadIdx.x;
+    f8[r * QBA_CT_THREADS + threadIdx.x] = (i < n && p.test(i)) ? 1 : 0;
+  }
+  uint32_t bits;
+  int32_t c;
+  const int32_t rank = qba_ct_rank<QBA_CT_THREADS>(flags, bits, c);
+  qba_ct_emit(p, bits, tbase + (int64_t)threadIdx.x * QBA_CT_ITEMS, offsets[tile] + rank, cap);
 }
 
 // Inputs of at most QBA_CS_MAX items in ONE launch of one workgroup (the
@@ -105,38 +122,17 @@ __global__ void __launch_bounds__(QBA_CT_THREADS)
 template <class Pred>
 __global__ void __launch_bounds__(QBA_CS_THREADS)
     qba_k_compact_small(Pred p, int64_t n, int64_t cap, int64_t *__restrict__ total) {
-  __shared__ int32_t wsum[QBA_CS_THREADS / 64];
   __shared__ uint32_t flags[QBA_CS_MAX / 4];
   uint8_t *f8 = reinterpret_cast<uint8_t *>(flags);
   for (int r = 0; r < QBA_CT_ITEMS; ++r) {
     const int64_t i = (int64_t)r * QBA_CS_THREADS + threadIdx.x;
     f8[i] = (i < n && p.test(i)) ? 1 : 0;
   }
-  __syncthreads();
-  const int64_t base = (int64_t)threadIdx.x * QBA_CT_ITEMS;
-  uint32_t bits = 0;
-#pragma unroll
-  for (int q = 0; q < QBA_CT_ITEMS / 4; ++q)
-    bits |= ((flags[threadIdx.x * (QBA_CT_ITEMS / 4) + q] * 0x01020408u) >> 24) << (4 * q);
-  const int32_t c = __popc(bits);
-  int32_t incl = c;
-  const int lane = threadIdx.x & 63;
-  for (int off = 1; off < 64; off <<= 1) {
-    const int32_t y = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += y;
-  }
-  if (lane == 63) wsum[threadIdx.x >> 6] = incl;
-  __syncthreads();
-  int32_t wbase = 0;
-  for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) wbase += wsum[w];
-  int64_t pos = wbase + incl - c;
+  uint32_t bits;
+  int32_t c;
+  const int64_t pos = qba_ct_rank<QBA_CS_THREADS>(flags, bits, c);
   if (threadIdx.x == QBA_CS_THREADS - 1) *total = pos + c;
-  while (bits) {
-    const int k = __ffs(bits) - 1;
-    bits &= bits - 1;
-    if (pos < cap) p.emit(base + k, pos);
-    ++pos;
-  }
+  qba_ct_emit(p, bits, (int64_t)threadIdx.x * QBA_CT_ITEMS, pos, cap);
 }
 
 // Runs the three passes on `stream`, then waits and returns the total in *count_host.

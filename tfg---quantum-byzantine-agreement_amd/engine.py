@@ -31,6 +31,39 @@ def _u64(x) -> int:
     return int(x) & ((1 << 64) - 1)
 
 
+def _row_ld(nbytes: int) -> int:
+    """Row pitch of a list buffer whose rows hold ``nbytes`` bytes."""
+    # rows start 4 KiB-aligned: the 8-B-per-lane row stores then never
+    # straddle a partial line at a row start (1.3% over 64-B alignment at
+    # n = 11, measured in round 2)
+    return max(4096, (nbytes + 4095) // 4096 * 4096)
+
+
+def _packet_stage(stage: np.ndarray, off: int, order, rows) -> int:
+    """Writes the stage of one packet request, [order | rows] (every row
+    len(order) entries), into ``stage`` at ``off``; returns the offset behind it."""
+    ln = len(order)
+    stage[off:off + ln] = order
+    for t in rows:
+        off += ln
+        stage[off:off + ln] = t if isinstance(t, np.ndarray) else np.fromiter(t, dtype=np.int64, count=ln)
+    return off + ln
+
+
+def _packet_result(out: np.ndarray, o: int, ln: int, m: int, who: str) -> Tuple[np.ndarray, bool]:
+    """(own as the int64 array it travels as, verdict) from one packet's
+    output at out[o:]: own (ln), bad index, violation among the rows,
+    violation of own, eq (m), as qba_check_packet writes them."""
+    e = o + ln
+    if out[e]:
+        raise QbaError(f"{who}: index outside the list")
+    eq = out[e + 3:e + 3 + m]
+    ok = not out[e + 1] and not out[e + 2] and bool(np.all((eq == 0) | (eq == ln)))
+    if m and not ln:  # every tuple empty: the set is {()}, vacuously consistent
+        ok = True
+    return out[o:e], ok
+
+
 @dataclass
 class Counts:
     """Count-mode result of one pass (see qba.h): int64 device tensors."""
@@ -144,18 +177,12 @@ class Engine:
 
     # -- buffers -----------------------------------------------------------------
     def alloc_lists(self, n: int, count: int) -> torch.Tensor:
-        # rows start 4 KiB-aligned: the 8-B-per-lane row stores then never
-        # straddle a partial line at a row start (1.3% over 64-B alignment at
-        # n = 11, measured in round 2)
-        ld = max(4096, (count + 4095) // 4096 * 4096)
-        return torch.empty((n + 1, ld), dtype=torch.uint8, device=self.device)
+        return torch.empty((n + 1, _row_ld(count)), dtype=torch.uint8, device=self.device)
 
     def alloc_packed(self, n: int, count: int) -> torch.Tensor:
         """Nibble rows (qba.h "packed lists"): (count + 1) // 2 bytes per row,
         rows 4 KiB-aligned like alloc_lists."""
-        nb = (count + 1) // 2
-        ld = max(4096, (nb + 4095) // 4096 * 4096)
-        return torch.empty((n + 1, ld), dtype=torch.uint8, device=self.device)
+        return torch.empty((n + 1, _row_ld((count + 1) // 2)), dtype=torch.uint8, device=self.device)
 
     def alloc_counts(self, n: int) -> Counts:
         _, w = self.sizes(n)
@@ -242,13 +269,9 @@ class Engine:
         per-instance counts [n_inst, ...]."""
         self.prepare(n)
         _, w = self.sizes(n)
-        # rows start 4 KiB-aligned: the 8-B-per-lane row stores then never
-        # straddle a partial line at a row start (1.3% over 64-B alignment at
-        # n = 11, measured in round 2)
         nb = (count + 1) // 2 if packed else count
-        ld = max(4096, (nb + 4095) // 4096 * 4096)
         if lists is None:
-            lists = torch.empty((n_inst, n + 1, ld), dtype=torch.uint8, device=self.device)
+            lists = torch.empty((n_inst, n + 1, _row_ld(nb)), dtype=torch.uint8, device=self.device)
         if lists.dim() != 3 or lists.shape[:2] != (n_inst, n + 1) or lists.stride(2) != 1:
             raise QbaError("lists must be a uint8 [n_inst, n+1, ld] tensor")
         z = lambda *s: torch.empty(s, dtype=torch.int64, device=self.device)  # noqa: E731
@@ -473,9 +496,7 @@ class Engine:
                 lists.stride(1) != 1 or lists.shape[1] < count:
             raise QbaError("lists must be a uint8 [>= rows, >= count] device tensor")
         if packed is None:
-            nb = (count + 1) // 2
-            packed = torch.empty((rows, max(4096, (nb + 4095) // 4096 * 4096)), dtype=torch.uint8,
-                                 device=self.device)
+            packed = torch.empty((rows, _row_ld((count + 1) // 2)), dtype=torch.uint8, device=self.device)
         ldp = self._packed_ok(packed, rows, count)
         bad = torch.empty(1, dtype=torch.int64, device=self.device)
         call("qba_lists_pack", self.ctx, _ptr(lists), lists.stride(0), rows, count, _ptr(packed), ldp,
@@ -489,8 +510,7 @@ class Engine:
         """Nibble rows -> byte rows [rows, ld] on the device."""
         ldp = self._packed_ok(packed, rows, count)
         if out is None:
-            out = torch.empty((rows, max(4096, (count + 4095) // 4096 * 4096)), dtype=torch.uint8,
-                              device=self.device)
+            out = torch.empty((rows, _row_ld(count)), dtype=torch.uint8, device=self.device)
         if out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] < rows or out.stride(1) != 1 or \
                 out.shape[1] < count:
             raise QbaError("out must be a uint8 [>= rows, >= count] device tensor")
@@ -587,21 +607,12 @@ class Engine:
         (Cond1 stays with the caller)."""
         ln, m = len(order), len(rows)
         stage = np.empty(ln * (m + 1), np.int64)
-        stage[:ln] = order
-        if m and ln:
-            for a, t in enumerate(rows):
-                stage[ln * (a + 1):ln * (a + 2)] = t if isinstance(t, np.ndarray) else \
-                    np.fromiter(t, dtype=np.int64, count=ln)
+        _packet_stage(stage, 0, order, rows)
         o = np.empty(ln + 3 + m, np.int64)
         call("qba_check_packet_host", self.ctx, _ptr(li), li.numel(), stage.ctypes.data, m, ln, int(v), int(w),
              o.ctypes.data, self.stream())
-        if o[ln]:
-            raise QbaError("qba_check_packet: index outside the list")
-        eq = o[ln + 3:]
-        ok = not o[ln + 1] and not o[ln + 2] and bool(np.all((eq == 0) | (eq == ln)))
-        if m and not ln:  # every tuple empty: the set is {()}, vacuously consistent
-            ok = True
-        return tuple(o[:ln].tolist()), ok
+        own, ok = _packet_result(o, 0, ln, m, "qba_check_packet")
+        return tuple(own.tolist()), ok
 
     def check_packets(self, li: torch.Tensor, reqs: Sequence[Tuple[np.ndarray, Sequence, int]],
                       w: int) -> list:
@@ -612,29 +623,18 @@ class Engine:
         if not reqs:
             return []
         dims = [(len(o), len(r)) for o, r, _ in reqs]
-        nin = sum(ln * (m + 1) for ln, m in dims)
-        stage = np.empty(max(nin, 1), np.int64)
+        stage = np.empty(max(sum(ln * (m + 1) for ln, m in dims), 1), np.int64)
         desc = np.empty(3 * len(reqs), np.int64)
         off = 0
         for i, ((order, rows, v), (ln, m)) in enumerate(zip(reqs, dims)):
             desc[3 * i:3 * i + 3] = (m, ln, int(v))
-            stage[off:off + ln] = order
-            for a, t in enumerate(rows):
-                stage[off + ln * (a + 1):off + ln * (a + 2)] = t if isinstance(t, np.ndarray) else \
-                    np.fromiter(t, dtype=np.int64, count=ln)
-            off += ln * (m + 1)
+            off = _packet_stage(stage, off, order, rows)
         out = np.empty(sum(ln + 3 + m for ln, m in dims), np.int64)
         call("qba_check_packets_host", self.ctx, _ptr(li), li.numel(), stage.ctypes.data, desc.ctypes.data,
              len(reqs), int(w), out.ctypes.data, self.stream())
         res, o = [], 0
         for ln, m in dims:
-            if out[o + ln]:
-                raise QbaError("qba_check_packets_host: index outside the list")
-            eq = out[o + ln + 3:o + ln + 3 + m]
-            ok = not out[o + ln + 1] and not out[o + ln + 2] and bool(np.all((eq == 0) | (eq == ln)))
-            if m and not ln:  # every tuple empty: the set is {()}, vacuously consistent
-                ok = True
-            own = out[o:o + ln]
+            own, ok = _packet_result(out, o, ln, m, "qba_check_packets_host")
             res.append((tuple(own.tolist()), ok, own))
             o += ln + 3 + m
         return res

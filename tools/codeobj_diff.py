@@ -12,7 +12,9 @@ byte-identical and the sets of kernel symbols (*.kd) equal.  Symbol-name
 tables are not compared: each object's __hip_cuid_* name hashes its source.
 Prints one line per object; exit status 1 on any difference between paired
 objects or on a removed one (an added object alone is not a difference in
-the kernels the old build had).  No GPU needed.
+the kernels the old build had).  Under an object that differs or was added,
+one line per kernel gives the descriptor's VGPRs, SGPRs, static LDS and
+scratch of both builds.  No GPU needed.
 """
 import hashlib
 import sys
@@ -26,7 +28,7 @@ SECTIONS = (".text", ".rodata", ".note")
 
 def summary(elf: bytes):
     secs = {s["name"]: elf[s["off"]:s["off"] + s["size"]] for s in _sections(elf) if s["name"] in SECTIONS}
-    return secs, frozenset(_descriptors(elf))
+    return secs, _descriptors(elf)
 
 
 def _line(i, secs, kernels, verdict):
@@ -34,6 +36,13 @@ def _line(i, secs, kernels, verdict):
     text = secs.get(".text", b"")
     return (f"object {i:2d}: {len(kernels):3d} kernels, .text {len(text):8d} B "
             f"sha256 {hashlib.sha256(text).hexdigest()[:12]}  {verdict}  [{first[:40]}]")
+
+
+def _kernels(old: dict, new: dict):
+    """Per kernel of a changed object: the descriptor fields in the old and the new build."""
+    fmt = lambda d: "-" if d is None else "vgpr {vgprs:3d} sgpr {sgprs:3d} lds {lds:6d} scratch {scratch}".format(**d)  # noqa: E731
+    for k in sorted(set(old) | set(new)):
+        print(f"    {k}\n      old: {fmt(old.get(k))}\n      new: {fmt(new.get(k))}")
 
 
 def main(old: str, new: str) -> int:
@@ -48,6 +57,7 @@ def main(old: str, new: str) -> int:
     for i, (x, y) in enumerate(pairs):
         if x is None:
             print(_line(i, *y, "added"))
+            _kernels({}, y[1])
             continue
         if y is None:
             print(_line(i, *x, "REMOVED"))
@@ -55,10 +65,12 @@ def main(old: str, new: str) -> int:
             continue
         (sx, kx), (sy, ky) = x, y
         diff = [n for n in SECTIONS if sx.get(n) != sy.get(n)]
-        if kx != ky:
-            diff.append(f"kernels -{len(kx - ky)} +{len(ky - kx)}")
+        if set(kx) != set(ky):
+            diff.append(f"kernels -{len(set(kx) - set(ky))} +{len(set(ky) - set(kx))}")
         bad |= bool(diff)
         print(_line(i, sy, ky, "DIFFERENT: " + ", ".join(diff) if diff else "equal"))
+        if diff:
+            _kernels(kx, ky)
     added = sum(1 for x, _ in pairs if x is None)
     print("DIFFERENT" if bad else
           f"all {len(a)} code objects of the old build equal (.text, .rodata, .note, kernel names)"
