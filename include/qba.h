@@ -338,6 +338,40 @@ QBA_API int qba_montecarlo_curve_shape(int n_parties, int *waves, int64_t *lds_b
 QBA_API int qba_montecarlo_program_shape(qba_ctx *ctx, int n_parties, int curve, int *sampler, int *waves_compiled,
                                          int *waves_run, int64_t *lds_bytes, int *wgs_per_cu);
 
+/* Qubit-flip noise: every one of the (n+1)*nQ
+ * measured bits of an entry flips independently with probability
+ * flip_q16 / 65536, 0 <= flip_q16 <= 65535, before anything looks at the
+ * entry.  Entry e of the instance keyed key = seed_base + i draws
+ *   word(t) = output word t % 4 of philox4x32-10(ctr = {e_lo, e_hi, t / 4,
+ *             0x4E4F4953}, key = {key_lo, key_hi}),
+ * folds the bits of k = flip_q16 from its lowest set bit j0 upwards into 64
+ * bits r, starting from 0:  x = word(2s) | word(2s+1) << 32;  r = bit j0 + s of
+ * k ? r | x : r & x  for s = 0 .. 15 - j0, and XORs (r >> 4g) & (w - 1) into
+ * the value of group g = 0 .. n.  Values stay below w.  The flips of entry e
+ * depend on (key, e, flip_q16) alone.
+ *
+ * The two noisy Monte-Carlo calls are qba_montecarlo_sampled and
+ * qba_montecarlo_curve_sampled on the noisy entries, drawn and flipped inside
+ * the kernel: checks, their order, row layout, asynchrony and capture legality
+ * are those calls'; flip_q16 > 65535 is QBA_EINVAL, checked after the count(s)
+ * and before ctx.  flip_q16 == 0 runs the noiseless kernel. */
+QBA_API int qba_montecarlo_sampled_noisy(qba_ctx *ctx, int n_parties, int n_dishonest, uint64_t seed_base,
+                                         int64_t n_instances, uint64_t count, uint32_t flip_q16, int32_t *out_dev,
+                                         qba_stream stream);
+QBA_API int qba_montecarlo_curve_sampled_noisy(qba_ctx *ctx, int n_parties, int n_dishonest, uint64_t seed_base,
+                                               int64_t n_instances, const uint32_t *counts_host, int n_counts,
+                                               uint32_t flip_q16, int32_t *out_dev, qba_stream stream);
+/* The same flips XORed in place into byte rows in the layout of
+ * qba_sample_check_batched (instance i at lists_dev + i*inst_stride, rows ld
+ * apart, entries [0, count); that call's checks of them, after flip_q16 >
+ * 65535, which is checked first): the noisy lists themselves, from
+ * qba_sample_check_batched or qba_sample before it.  Bytes at columns >= count
+ * are not touched.  flip_q16 == 0 launches nothing.  Needs no program.
+ * Asynchronous on `stream`. */
+QBA_API int qba_noise_apply_batched(qba_ctx *ctx, int n_parties, uint64_t seed_base, int64_t n_instances,
+                                    uint64_t count, uint32_t flip_q16, uint8_t *lists_dev, uint64_t ld,
+                                    uint64_t inst_stride, qba_stream stream);
+
 /* The result rows of the calls above reduced on the device (DESIGN.md section
  * 13.3).  rows_dev is [n_slices][n_instances][4 + 5*(n+1)] int32, contiguous:
  * what a curve call writes, or with n_slices == 1 a single-count call.

@@ -263,9 +263,10 @@ struct QbaMcCounts {
   int n;
 };
 // That envelope for qba_montecarlo_curve_sampled / _lists, `bad_count` being
-// the checks of the checkpoint list; fills `cv`
+// the checks of the checkpoint list, then `bad_other` (what else is wrong
+// before ctx is looked at; NULL: nothing); fills `cv`
 int qba_mc_curve_check(const char *who, qba_ctx *ctx, int n, int n_dis, int64_t n_inst, const uint32_t *counts,
-                       int n_counts, const void *out, QbaMcCounts *cv);
+                       int n_counts, const void *out, QbaMcCounts *cv, const char *bad_other = nullptr);
 
 static inline int qba_nq(int n) {  // ceil(log2(n+1)), tfg.py:317
   int q = 0;

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "qba_internal.h"
+#include "qba_noise.h"
 
 struct QbaLaunch {
   int n;
@@ -35,7 +36,8 @@ struct QbaBatch {
 
 // qba_montecarlo_sampled and qba_montecarlo_curve_sampled (qba_mc_kern.h);
 // fields have the kernel arguments' types.  The single-count call is the one
-// with one checkpoint and `curve` 0, which picks its kernel.
+// with one checkpoint and `curve` 0, which picks its kernel.  `noise` is read by
+// the noisy kernels alone (qba_montecarlo_*_noisy with flip_q16 > 0).
 struct QbaMc {
   const char *who;  // the exported function, for messages
   const QbaProgramSet *ps;
@@ -46,6 +48,7 @@ struct QbaMc {
   hipStream_t stream;
   QbaMcCounts counts;
   int curve;
+  QbaNoise noise;
 };
 
 template <int NP>
@@ -57,6 +60,9 @@ template <int NP>
 int qba_launch_batched(qba_ctx *ctx, const QbaBatch &B);
 template <int NP>
 int qba_launch_mc(qba_ctx *ctx, const QbaMc &M);
+// the same through the noisy kernels (qba_mc_noise_inst.hip)
+template <int NP>
+int qba_launch_mc_noisy(qba_ctx *ctx, const QbaMc &M);
 // qba_montecarlo_shape, or (curve) qba_montecarlo_curve_shape
 template <int NP>
 void qba_mc_shape_n(int curve, int *waves, int64_t *lds, int *wgs);

@@ -97,24 +97,72 @@ static int mc_sampled(qba_ctx *ctx, int n, QbaMc &M) {
   if (M.n_inst == 0) return QBA_OK;
   if (int rc = qba_set_device(ctx)) return rc;
   M.ps = (const QbaProgramSet *)ctx->prog_dev[n];
+  if (M.noise.steps)
+    return with_n(n, [&](auto k) { return qba_launch_mc_noisy<decltype(k)::value>(ctx, M); });
   return with_n(n, [&](auto k) { return qba_launch_mc<decltype(k)::value>(ctx, M); });
+}
+
+// The single-count and the curve call, noiseless (flip_q16 0: the noiseless
+// kernel) or noisy, behind the names they are exported under.
+static const char *bad_flip(uint32_t flip_q16) { return flip_q16 > 65535u ? "flip_q16 must be <= 65535" : nullptr; }
+
+static int mc_one(const char *who, qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst, uint64_t count,
+                  uint32_t flip_q16, int32_t *out, qba_stream stream) {
+  QbaMc M{who, nullptr, seed_base, n_inst, n_dis, out, (hipStream_t)stream, {{(uint32_t)count}, 1}, 0, {}};
+  const char *bad = count >> 31 ? "count must be < 2^31" : bad_flip(flip_q16);
+  if (int rc = qba_mc_check(who, ctx, n, n_dis, bad, n_inst, out)) return rc;
+  if (flip_q16) M.noise = qba_noise_of(flip_q16);
+  return mc_sampled(ctx, n, M);
+}
+
+static int mc_curve(const char *who, qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
+                    const uint32_t *counts, int n_counts, uint32_t flip_q16, int32_t *out, qba_stream stream) {
+  QbaMc M{who, nullptr, seed_base, n_inst, n_dis, out, (hipStream_t)stream, {}, 1, {}};
+  if (int rc = qba_mc_curve_check(who, ctx, n, n_dis, n_inst, counts, n_counts, out, &M.counts, bad_flip(flip_q16)))
+    return rc;
+  if (flip_q16) M.noise = qba_noise_of(flip_q16);
+  return mc_sampled(ctx, n, M);
 }
 
 extern "C" int qba_montecarlo_sampled(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
                                       uint64_t count, int32_t *out, qba_stream stream) {
-  const char *who = "qba_montecarlo_sampled";
-  QbaMc M{who, nullptr, seed_base, n_inst, n_dis, out, (hipStream_t)stream, {{(uint32_t)count}, 1}, 0};
-  if (int rc = qba_mc_check(who, ctx, n, n_dis, count >> 31 ? "count must be < 2^31" : nullptr, n_inst, out)) return rc;
-  return mc_sampled(ctx, n, M);
+  return mc_one("qba_montecarlo_sampled", ctx, n, n_dis, seed_base, n_inst, count, 0u, out, stream);
+}
+
+extern "C" int qba_montecarlo_sampled_noisy(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
+                                            uint64_t count, uint32_t flip_q16, int32_t *out, qba_stream stream) {
+  return mc_one("qba_montecarlo_sampled_noisy", ctx, n, n_dis, seed_base, n_inst, count, flip_q16, out, stream);
 }
 
 extern "C" int qba_montecarlo_curve_sampled(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
                                             const uint32_t *counts, int n_counts, int32_t *out,
                                             qba_stream stream) {
-  const char *who = "qba_montecarlo_curve_sampled";
-  QbaMc M{who, nullptr, seed_base, n_inst, n_dis, out, (hipStream_t)stream, {}, 1};
-  if (int rc = qba_mc_curve_check(who, ctx, n, n_dis, n_inst, counts, n_counts, out, &M.counts)) return rc;
-  return mc_sampled(ctx, n, M);
+  return mc_curve("qba_montecarlo_curve_sampled", ctx, n, n_dis, seed_base, n_inst, counts, n_counts, 0u, out,
+                  stream);
+}
+
+extern "C" int qba_montecarlo_curve_sampled_noisy(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
+                                                  const uint32_t *counts, int n_counts, uint32_t flip_q16,
+                                                  int32_t *out, qba_stream stream) {
+  return mc_curve("qba_montecarlo_curve_sampled_noisy", ctx, n, n_dis, seed_base, n_inst, counts, n_counts, flip_q16,
+                  out, stream);
+}
+
+// The flips of the noisy Monte-Carlo calls into lists in the layout of
+// qba_sample_check_batched, in place (qba_noise.hip); its argument checks,
+// after flip_q16.  Needs no program: it samples nothing.
+extern "C" int qba_noise_apply_batched(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst, uint64_t count,
+                                       uint32_t flip_q16, uint8_t *lists, uint64_t ld, uint64_t inst_stride,
+                                       qba_stream stream) {
+  const char *who = "qba_noise_apply_batched";
+  if (const char *bad = bad_flip(flip_q16)) return qba_fail(QBA_EINVAL, std::string(who) + ": " + bad);
+  if (int rc = check_common(ctx, n, lists, count, ld, who)) return rc;
+  if (n_inst < 0 || (n_inst > 1 && inst_stride < (uint64_t)(n + 1) * ld) || (inst_stride & 3) ||
+      count >= (1ull << 31))
+    return qba_fail(QBA_EINVAL, std::string(who) + ": bad arguments (inst_stride >= (n+1)*ld, "
+                                "multiple of 4; count < 2^31)");
+  if (n_inst == 0 || count == 0 || flip_q16 == 0) return QBA_OK;
+  return qba_launch_noise_apply(n, seed_base, n_inst, count, flip_q16, lists, ld, inst_stride, (hipStream_t)stream);
 }
 
 static int mc_shape(const char *who, int n, int curve, int *waves, int64_t *lds_bytes, int *wgs_per_cu) {

@@ -210,8 +210,9 @@ static const char *bad_counts(const uint32_t *counts, int n_counts) {
 }
 
 int qba_mc_curve_check(const char *who, qba_ctx *ctx, int n, int n_dis, int64_t n_inst, const uint32_t *counts,
-                       int n_counts, const void *out, QbaMcCounts *cv) {
-  if (int rc = qba_mc_check(who, ctx, n, n_dis, bad_counts(counts, n_counts), n_inst, out)) return rc;
+                       int n_counts, const void *out, QbaMcCounts *cv, const char *bad_other) {
+  const char *bad = bad_counts(counts, n_counts);
+  if (int rc = qba_mc_check(who, ctx, n, n_dis, bad ? bad : bad_other, n_inst, out)) return rc;
   *cv = QbaMcCounts{};
   for (int j = 0; j < n_counts; ++j) cv->c[j] = counts[j];
   cv->n = n_counts;

@@ -349,19 +349,47 @@ class Engine:
             raise QbaError(f"lists rows overlap: need stride(1) >= {need} and stride(0) >= (n+1)*stride(1)")
         return lists, n_inst, ld, stride
 
+    @staticmethod
+    def _check_flip(flip_q16: int) -> int:
+        if not 0 <= int(flip_q16) <= 65535:
+            raise QbaError("flip_q16 must be in [0, 65535]")
+        return int(flip_q16)
+
     def montecarlo_sampled(self, n: int, n_dishonest: int, seed_base: int, n_inst: int, count: int,
-                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                           out: Optional[torch.Tensor] = None, flip_q16: int = 0) -> torch.Tensor:
         """n_inst instances (key seed_base + i) of `count` entries sampled,
         distilled and decided in one kernel (qba_montecarlo_sampled): the rows
         of protocol_batched(sample_check_batched(...)), int32
-        [n_inst, 4 + 5*(n+1)], with no list buffer and no count tables."""
+        [n_inst, 4 + 5*(n+1)], with no list buffer and no count tables.
+        ``flip_q16=k > 0`` (qba_montecarlo_sampled_noisy): every measured bit of
+        an entry flips with probability k / 65536 first (montecarlo.noise_masks)."""
         self._check_n(n)
         self._check_curve(n, n_dishonest, n_inst, [count])
+        flip = self._check_flip(flip_q16)
         self.prepare(n)
         out = self._rows_out(n, n_inst, out)
-        call("qba_montecarlo_sampled", self.ctx, n, n_dishonest, _u64(seed_base), n_inst, count, _ptr(out),
-             self.stream())
+        if flip:
+            call("qba_montecarlo_sampled_noisy", self.ctx, n, n_dishonest, _u64(seed_base), n_inst, count, flip,
+                 _ptr(out), self.stream())
+        else:
+            call("qba_montecarlo_sampled", self.ctx, n, n_dishonest, _u64(seed_base), n_inst, count, _ptr(out),
+                 self.stream())
         return out
+
+    def noise_apply(self, n: int, seed_base: int, lists: torch.Tensor, count: int, flip_q16: int) -> torch.Tensor:
+        """XOR the flips of ``flip_q16`` (montecarlo.noise_masks under key
+        seed_base + i) into columns [0, count) of the uint8 [n_inst, n+1, ld]
+        device lists of sample_check_batched, in place
+        (qba_noise_apply_batched); returns ``lists``."""
+        self._check_n(n)
+        flip = self._check_flip(flip_q16)
+        if not isinstance(lists, torch.Tensor) or lists.dtype != torch.uint8 or lists.dim() != 3 or \
+                lists.shape[1] != n + 1 or lists.device != self.device or lists.stride(2) != 1 or \
+                lists.shape[2] < count:
+            raise QbaError("lists must be a uint8 [n_inst, n+1, >= count] device tensor with unit column stride")
+        call("qba_noise_apply_batched", self.ctx, n, _u64(seed_base), lists.shape[0], count, flip, _ptr(lists),
+             lists.stride(1), lists.stride(0), self.stream())
+        return lists
 
     def montecarlo_lists(self, n: int, n_dishonest: int, seed_base: int, lists, count: int,
                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -380,17 +408,23 @@ class Engine:
 
     # -- a whole sizeL curve in one pass (qba_montecarlo_curve_*) ------------------
     def montecarlo_curve_sampled(self, n: int, n_dishonest: int, seed_base: int, n_inst: int, counts,
-                                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                                 out: Optional[torch.Tensor] = None, flip_q16: int = 0) -> torch.Tensor:
         """The n_inst instances of montecarlo_sampled decided at every count of
         the strictly increasing ``counts`` (at most 32) in one pass over their
         entries (qba_montecarlo_curve_sampled): int32 [len(counts), n_inst,
-        4 + 5*(n+1)], slice j word for word montecarlo_sampled(count=counts[j])."""
+        4 + 5*(n+1)], slice j word for word montecarlo_sampled(count=counts[j]),
+        with ``flip_q16`` as there (qba_montecarlo_curve_sampled_noisy)."""
         self._check_n(n)
         cs = self._check_curve(n, n_dishonest, n_inst, counts)
+        flip = self._check_flip(flip_q16)
         self.prepare(n)
         out = self._rows_out(n, n_inst, out, len(cs))
-        call("qba_montecarlo_curve_sampled", self.ctx, n, n_dishonest, _u64(seed_base), n_inst,
-             (C.c_uint32 * len(cs))(*cs), len(cs), _ptr(out), self.stream())
+        if flip:
+            call("qba_montecarlo_curve_sampled_noisy", self.ctx, n, n_dishonest, _u64(seed_base), n_inst,
+                 (C.c_uint32 * len(cs))(*cs), len(cs), flip, _ptr(out), self.stream())
+        else:
+            call("qba_montecarlo_curve_sampled", self.ctx, n, n_dishonest, _u64(seed_base), n_inst,
+                 (C.c_uint32 * len(cs))(*cs), len(cs), _ptr(out), self.stream())
         return out
 
     def montecarlo_curve_lists(self, n: int, n_dishonest: int, seed_base: int, lists, counts,

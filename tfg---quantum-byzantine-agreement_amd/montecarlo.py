@@ -32,6 +32,12 @@ A whole sizeL curve (:func:`curve`, ``Engine.montecarlo_curve_sampled`` /
 pass: the lists at sizeL = c are the first c columns of the lists at any larger
 sizeL, and those reductions are monotone.  :func:`curve_host` is its
 specification.
+
+Qubit-flip noise (``flip_q16=k`` on the calls below):
+every measured bit of an entry flips independently with probability k / 65536
+before anything looks at the entry.  :func:`noise_masks` is the definition;
+the fused kernels draw the same flips inside (``Engine.montecarlo_sampled(...,
+flip_q16=k)``), and ``Engine.noise_apply`` XORs them into device lists.
 """
 from __future__ import annotations
 
@@ -45,6 +51,7 @@ from .countmode import CountParty
 
 MASK64 = (1 << 64) - 1
 CTR_TAG = 0x51424150  # word 3 of every protocol counter; the sampler's is 0 or 1
+NOISE_TAG = 0x4E4F4953  # word 3 of every noise counter
 RNG_CAP = 64          # words one randint may draw
 ST_MAILBOX, ST_RNG, ST_RANGE = 1, 2, 4
 
@@ -61,6 +68,21 @@ def philox4x32(ctr, key: int):
     for _ in range(10):
         p0, p1 = _M0 * c0, _M1 * c2
         c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & _U32, (p0 >> 32) ^ c3 ^ k1, p0 & _U32
+        k0, k1 = (k0 + _W0) & _U32, (k1 + _W1) & _U32
+    return c0, c1, c2, c3
+
+
+def _philox4x32_entries(e: np.ndarray, c2: int, c3: int, key: int):
+    """:func:`philox4x32` of the counters ``(e_lo, e_hi, c2, c3)`` for a uint64
+    array ``e`` at once: four uint64 arrays of 32-bit words."""
+    u32 = np.uint64(_U32)
+    c0, c1 = e & u32, e >> np.uint64(32)
+    c2, c3 = np.full_like(e, c2), np.full_like(e, c3)
+    k0, k1 = key & _U32, (key >> 32) & _U32
+    for _ in range(10):
+        p0, p1 = np.uint64(_M0) * c0, np.uint64(_M1) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0), p1 & u32, \
+            (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1), p0 & u32
         k0, k1 = (k0 + _W0) & _U32, (k1 + _W1) & _U32
     return c0, c1, c2, c3
 
@@ -135,8 +157,50 @@ def _mask(values) -> int:
     return m
 
 
+def _check_flip(flip_q16: int) -> int:
+    k = int(flip_q16)
+    if not 0 <= k <= 65535:
+        raise ValueError("flip_q16 must be in [0, 65535]")
+    return k
+
+
+def noise_masks(n: int, key: int, count: int, flip_q16: int) -> np.ndarray:
+    """The flips of the entries [0, count) of the instance keyed ``key`` at flip
+    probability k / 65536, k = ``flip_q16``: uint8 [n+1, count], the value XORed
+    into group g of entry e.  With word(t) = output word t % 4 of
+    ``philox4x32((e_lo, e_hi, t / 4, NOISE_TAG), key)`` and j0 the lowest set
+    bit of k, 64 bits r start at 0 and take, for s = 0 .. 15 - j0,
+    ``x = word(2s) | word(2s+1) << 32; r = r | x if bit j0 + s of k else r & x``
+    (one step maps a bit's probability q to (bit + q) / 2, so every bit of r is
+    1 with probability exactly k / 65536); the mask of group g is
+    ``(r >> 4g) & (w - 1)``.  k = 0 draws nothing."""
+    k = _check_flip(flip_q16)
+    g, w = n + 1, 1 << _nq(n)
+    out = np.zeros((g, int(count)), np.uint8)
+    if k == 0:
+        return out
+    j0 = (k & -k).bit_length() - 1
+    e = np.arange(int(count), dtype=np.uint64)
+    r = np.zeros(int(count), np.uint64)
+    blk = None
+    for s in range(16 - j0):
+        if s % 2 == 0:
+            blk = _philox4x32_entries(e, s // 2, NOISE_TAG, int(key) & MASK64)
+        x = blk[2 * (s % 2)] | blk[2 * (s % 2) + 1] << np.uint64(32)
+        r = r | x if (k >> (j0 + s)) & 1 else r & x
+    for i in range(g):
+        out[i] = (r >> np.uint64(4 * i)) & np.uint64(w - 1)
+    return out
+
+
+def noisy_lists(n: int, key: int, lists, flip_q16: int) -> np.ndarray:
+    """``lists`` [n+1, count] with :func:`noise_masks` XORed in (a new uint8 array)."""
+    L = np.array(lists, dtype=np.uint8).reshape(n + 1, -1)
+    return L ^ noise_masks(n, key, L.shape[1], flip_q16)
+
+
 def run_host(n: int, sizeL: int, n_dishonest: int, n_inst: int, seed_base: int, engine, lists=None,
-             party_cls=None, rng_factory: Optional[Callable] = None) -> np.ndarray:
+             party_cls=None, rng_factory: Optional[Callable] = None, flip_q16: int = 0) -> np.ndarray:
     """The specification of qba_protocol_batched: CountParty under
     ``protocol.run_local`` (LocalWorld's barrier-epoch delivery: a round's inbox
     is everything sent in the previous epoch, in (source, sequence) order,
@@ -147,7 +211,12 @@ def run_host(n: int, sizeL: int, n_dishonest: int, n_inst: int, seed_base: int, 
     engine); ``lists`` injects [n_inst, n+1, sizeL] values instead of sampling.
     ``party_cls`` (a CountParty subclass) and ``rng_factory`` ((key, rank) ->
     rng) are observation seams for tests.  Returns int32 [n_inst, out_words(n)].
+
+    ``flip_q16 > 0``: :func:`noisy_lists` of the lists the instance would have
+    used (injected, or else sampled by ``engine.sample(n, key, 0, sizeL)``,
+    which the engine must then offer), then the same.
     """
+    flip = _check_flip(flip_q16)
     out = np.zeros((n_inst, out_words(n)), np.int32)
     make = rng_factory or ProtocolRng
     for i in range(n_inst):
@@ -159,7 +228,11 @@ def run_host(n: int, sizeL: int, n_dishonest: int, n_inst: int, seed_base: int, 
             rngs.append(make(key, rank))
             return rngs[-1]
 
-        run = protocol.run_local(n, sizeL, n_dishonest, engine, lists=None if lists is None else lists[i],
+        mine = None if lists is None else lists[i]
+        if flip and sizeL > 0:
+            clean = engine.sample(n, key, 0, sizeL) if mine is None else np.asarray(mine)[:, :sizeL]
+            mine = noisy_lists(n, key, _host_lists(clean, sizeL), flip)
+        run = protocol.run_local(n, sizeL, n_dishonest, engine, lists=mine,
                                  list_seed=key, party_cls=_recording(party_cls or CountParty, parties),
                                  rng_factory=factory)
         status = ST_RNG if any(getattr(r, "capped", False) for r in rngs) else 0
@@ -175,6 +248,14 @@ def run_host(n: int, sizeL: int, n_dishonest: int, n_inst: int, seed_base: int, 
             row[4 + 5 * r:9 + 5 * r] = (run.result["decisions"][r - 1], _mask(p.Vi) if r > 1 else 0,
                                         p.stats.accept, p.stats.reject, p.stats.sent)
     return out
+
+
+def _host_lists(lists, count: int) -> np.ndarray:
+    """Sampled lists (a device tensor or an array, rows possibly padded) as a
+    host array [n+1, count]."""
+    if hasattr(lists, "cpu"):
+        lists = lists.cpu().numpy()
+    return np.asarray(lists)[:, :count]
 
 
 def summarize(n: int, out: np.ndarray) -> dict:
@@ -371,7 +452,7 @@ def masks_from_lists(n: int, lists) -> dict:
 
 
 def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, packed: bool = True,
-        batch: int = 4096, path: str = "tables", tally: bool = False, failures: int = 0) -> dict:
+        batch: int = 4096, path: str = "tables", tally: bool = False, failures: int = 0, flip_q16: int = 0) -> dict:
     """``runs`` independent instances on the device, ``batch`` at a time, batch
     at offset ``off`` under key ``seed + off``; only the result rows are copied
     to the host.  Returns :func:`summarize` of all rows.
@@ -387,16 +468,22 @@ def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, pack
     batch there; the result is :func:`summary_from_tally`, whose memory does
     not grow with ``runs``.  ``failures=F`` adds ``failed_runs``, the sorted
     indices of up to F runs without success (run i has key ``seed + i``), and
-    ``failed_total``, how many there were."""
+    ``failed_total``, how many there were.
+
+    ``flip_q16=k > 0`` (``path="fused"`` only; the tables path has no noisy
+    sampler): every measured bit flips with probability k / 65536."""
     if path not in ("tables", "fused"):
         raise ValueError("path is 'tables' or 'fused'")
+    noise = {"flip_q16": _check_flip(flip_q16)} if flip_q16 else {}
+    if noise and path == "tables":
+        raise ValueError("flip_q16 > 0 needs path='fused': the tables path has no noisy sampler")
     lists = None
 
     def decide(key, b, out=None):
         nonlocal lists
         into = {} if out is None else {"out": out[0]}
         if path == "fused":
-            return engine.montecarlo_sampled(n, n_dishonest, key, b, sizeL, **into)
+            return engine.montecarlo_sampled(n, n_dishonest, key, b, sizeL, **into, **noise)
         buf, counts = engine.sample_check_batched(n, key, b, sizeL, None if lists is None else lists[:b],
                                                   packed=packed)
         if lists is None:
@@ -405,30 +492,35 @@ def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, pack
     return _batches(n, 1, runs, batch, seed, engine, decide, tally, failures)[0]
 
 
-def curve_host(n: int, counts, n_dishonest: int, n_inst: int, seed_base: int, engine, lists=None) -> np.ndarray:
+def curve_host(n: int, counts, n_dishonest: int, n_inst: int, seed_base: int, engine, lists=None,
+               flip_q16: int = 0) -> np.ndarray:
     """The specification of the curve calls: the stack of :func:`run_host` at
     each count of ``counts``, int32 [len(counts), n_inst, out_words(n)].
     Injected ``lists`` [n_inst, n+1, >= max(counts)] are truncated to
-    ``[:, :, :c]`` for the count c."""
+    ``[:, :, :c]`` for the count c.  ``flip_q16`` as in :func:`run_host` (the
+    flips of entry e are the same at every count)."""
     counts = [int(c) for c in counts]
     li = None if lists is None else np.asarray(lists)
-    rows = [run_host(n, c, n_dishonest, n_inst, seed_base, engine, lists=None if li is None else li[:, :, :c])
+    noise = {"flip_q16": flip_q16} if flip_q16 else {}
+    rows = [run_host(n, c, n_dishonest, n_inst, seed_base, engine, lists=None if li is None else li[:, :, :c],
+                     **noise)
             for c in counts]
     return np.stack(rows) if rows else np.zeros((0, n_inst, out_words(n)), np.int32)
 
 
 def curve(n: int, counts, n_dishonest: int, runs: int, seed: int, engine, batch: int = 4096, tally: bool = False,
-          failures: int = 0) -> dict:
+          failures: int = 0, flip_q16: int = 0) -> dict:
     """The failure curve over sizeL: ``runs`` instances, ``batch`` at a time as
     :func:`run` keys them, each decided at every sizeL of the strictly
     increasing ``counts`` by one montecarlo_curve_sampled call per batch.
     Returns ``{sizeL: summarize(...)}`` in checkpoint order; the summary at
     sizeL = c is that of ``run(n, c, ..., path="fused")``.  ``tally`` and
-    ``failures`` as in :func:`run`, per checkpoint."""
+    ``failures`` as in :func:`run`, per checkpoint; ``flip_q16`` as there."""
     counts = [int(c) for c in counts]
+    noise = {"flip_q16": _check_flip(flip_q16)} if flip_q16 else {}
     if tally or failures:
         engine._check_curve(n, n_dishonest, 0, counts)  # before any device buffer: an empty list has no slice
 
     def decide(key, b, **into):
-        return engine.montecarlo_curve_sampled(n, n_dishonest, key, b, counts, **into)
+        return engine.montecarlo_curve_sampled(n, n_dishonest, key, b, counts, **into, **noise)
     return dict(zip(counts, _batches(n, len(counts), runs, batch, seed, engine, decide, tally, failures)))

@@ -75,6 +75,10 @@ def _args(argv):
     ap.add_argument("--failures", type=int, default=0, metavar="K",
                     help="with --runs: after each summary line, the indices of up to K runs without success, to "
                          "replay under key seed + index; implies --tally")
+    ap.add_argument("--flip", type=int, default=None, metavar="K",
+                    help="with --runs: every measured qubit flips with probability K / 65536, 0 <= K <= 65535 "
+                         "(montecarlo.noise_masks); implies --fused; with K > 0 the summary lines end in "
+                         "flip=K/65536")
     ap.add_argument("--quiet", action="store_true", help="print only the outcome")
     ap.add_argument("--timing", action="store_true", help="print the wall time of the run")
     ap.add_argument("--wire", action="store_true",
@@ -93,6 +97,12 @@ def _args(argv):
         ap.error("--failures: K >= 0")
     if (a.tally or a.failures) and a.runs is None:
         ap.error("--tally and --failures need --runs")
+    if a.flip is not None:
+        if a.runs is None:
+            ap.error("--flip needs --runs")
+        if not 0 <= a.flip <= 65535:
+            ap.error("--flip: K must be in [0, 65535] (out of 65536)")
+        a.fused = True
     return a
 
 
@@ -213,6 +223,9 @@ def _montecarlo(a, eng, size_l) -> int:
     seed = secrets.randbits(62) if a.seed is None else a.seed
     t0 = time.perf_counter()
     how = {"tally": True, "failures": a.failures} if a.tally or a.failures else {}
+    if a.flip:
+        how["flip_q16"] = a.flip
+    noise = f" flip={a.flip}/65536" if a.flip else ""
     if a.curve is not None:
         points = montecarlo.curve(a.parties, a.curve, a.nDishonest, a.runs, seed, eng, batch=a.batch, **how)
     else:
@@ -220,7 +233,7 @@ def _montecarlo(a, eng, size_l) -> int:
                                          path="fused" if a.fused else "tables", **how)}
     for c, s in points.items():
         print(f"Runs: {s['runs']} Successes: {s['successes']} Rate: {s['rate']:.6f} "
-              f"(n={a.parties}, sizeL={c}, dishonest={a.nDishonest}, empty-V_i runs={s['empty_vi_runs']})")
+              f"(n={a.parties}, sizeL={c}, dishonest={a.nDishonest}, empty-V_i runs={s['empty_vi_runs']}){noise}")
         if a.failures:
             print(f"Failed runs ({len(s['failed_runs'])} of {s['failed_total']}, key = seed + index, seed={seed}): "
                   + " ".join(str(i) for i in s["failed_runs"]))

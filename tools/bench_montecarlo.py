@@ -24,7 +24,14 @@ instances x n = 7 x sizeL = 1e5, 2 dishonest, on one GPU.
       wall time the two endings of a batch: tally + one [1, 32] copy +
       summary_from_tally against rows to host + summarize.
 
-(a), (b), (d), the --tally calls and the --curve pair are device-event times of single calls on warm code: median, min
+  --flip K  (repeatable) another mode, per --sizeL or per --curve: the noisy
+      fused call (qba_montecarlo_sampled_noisy, or the noisy curve call) at each
+      flip probability K / 65536 beside the noiseless call, which is timed first
+      and again last in the same session; K = 0 goes through the noisy entry
+      point and runs the noiseless kernel.  Reports noisy / noiseless at the
+      medians and the Philox blocks per entry the noise adds.
+
+(a), (b), (d), the --tally calls, the --flip calls and the --curve pair are device-event times of single calls on warm code: median, min
 and max over --repeats launches after --warmup launches.  (c) is host wall
 time around runs that end in device synchronisation (each reads its tables
 back).  Prints one JSON line; --out also writes it to a file.  No GPU: fails.
@@ -74,10 +81,17 @@ def main(argv=None) -> int:
     ap.add_argument("--tally", action="store_true",
                     help="time montecarlo_tally alone, montecarlo_sampled followed by it, and the rows-to-host "
                          "ending it replaces, at each --sizeL; nothing else is measured")
+    ap.add_argument("--flip", type=int, action="append", default=None, metavar="K",
+                    help="time the noisy fused call (with --curve: the noisy curve call) at flip probability "
+                         "K / 65536 beside the noiseless one; repeatable; nothing else is measured")
     a = ap.parse_args(argv)
 
     eng = importlib.import_module(f"{PKG}.engine").Engine(0)
-    if a.tally:
+    if a.flip:
+        shapes = ([sorted({int(c) for c in text.split(",")}) for text in a.curve] if a.curve
+                  else [[s] for s in (a.sizeL or [100_000])])
+        lines = [json.dumps(_measure_flip(a, eng, counts, bool(a.curve))) for counts in shapes]
+    elif a.tally:
         lines = [json.dumps(_measure_tally(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
     elif a.curve:
         lines = [json.dumps(_measure_curve(a, eng, sorted({int(c) for c in text.split(",")}))) for text in a.curve]
@@ -118,6 +132,50 @@ def _measure_curve(a, eng, counts) -> dict:
     # faster only where the min-max ranges do not overlap
     res["curve_faster"] = c["max_ms"] < s["min_ms"]
     res["separate_faster"] = s["max_ms"] < c["min_ms"]
+    return res
+
+
+def _measure_flip(a, eng, counts, curve: bool) -> dict:
+    """--flip: the noisy call at each K beside the noiseless call of the same session."""
+    import ctypes as C
+
+    import torch
+    em = importlib.import_module(f"{PKG}.engine")
+    n, nd, inst = a.parties, a.dishonest, a.instances
+    eng.prepare(n)
+    shape = (len(counts), inst, 4 + 5 * (n + 1)) if curve else (inst, 4 + 5 * (n + 1))
+    rows = torch.empty(shape, dtype=torch.int32, device=eng.device)
+    cs = (C.c_uint32 * len(counts))(*counts)
+
+    def noisy(k):  # the C entry point itself: the Engine sends k = 0 to the noiseless symbol
+        if curve:
+            em.call("qba_montecarlo_curve_sampled_noisy", eng.ctx, n, nd, a.seed, inst, cs, len(counts), k,
+                    em._ptr(rows), eng.stream())
+        else:
+            em.call("qba_montecarlo_sampled_noisy", eng.ctx, n, nd, a.seed, inst, counts[0], k, em._ptr(rows),
+                    eng.stream())
+
+    def clean():
+        if curve:
+            eng.montecarlo_curve_sampled(n, nd, a.seed, inst, counts, rows)
+        else:
+            eng.montecarlo_sampled(n, nd, a.seed, inst, counts[0], rows)
+
+    res = {"config": {"n": n, "counts" if curve else "sizeL": counts if curve else counts[0], "dishonest": nd,
+                      "instances": inst, "seed": a.seed, "device": torch.cuda.get_device_name(0)}}
+    res["noiseless"] = _events(clean, a.warmup, a.repeats)
+    ref = rows.clone()
+    res["flips"] = {}
+    for k in a.flip:
+        t = _events(lambda: noisy(k), a.warmup, a.repeats)
+        t["noise_blocks_per_entry"] = 0 if k == 0 else (16 - ((k & -k).bit_length() - 1) + 1) // 2
+        t["rows_equal_noiseless"] = bool(torch.equal(rows, ref))
+        res["flips"][str(k)] = t
+    res["noiseless_again"] = _events(clean, a.warmup, a.repeats)
+    base = min(res["noiseless"]["median_ms"], res["noiseless_again"]["median_ms"])
+    res["noiseless_spread_at_median"] = abs(res["noiseless"]["median_ms"] - res["noiseless_again"]["median_ms"]) / base
+    for t in res["flips"].values():
+        t["over_noiseless_at_median"] = t["median_ms"] / base
     return res
 
 
