@@ -235,6 +235,25 @@ QBA_API int qba_sample_check_batched_packed(qba_ctx *ctx, int n_parties, uint64_
                                             uint64_t ld, uint64_t inst_stride, int64_t *H_dev,
                                             int64_t *C_dev, int64_t *P_dev, qba_stream stream);
 
+/* The two calls above under qubit-flip noise: every measured bit of an entry
+ * flips with probability flip_q16 / 65536 (the flips of
+ * qba_montecarlo_sampled_noisy and qba_noise_apply_batched: entry e of
+ * instance i draws them under key seed_base + i) as the entry is sampled, so
+ * the rows written and the tables counted are those of the noisy entries --
+ * what the noiseless call followed by qba_noise_apply_batched leaves in the
+ * rows, with the tables to match.  flip_q16 = 0 launches the noiseless kernel;
+ * flip_q16 > 65535 is QBA_EINVAL, checked before ctx is looked at; the other
+ * arguments and checks are the noiseless calls'. */
+QBA_API int qba_sample_check_batched_noisy(qba_ctx *ctx, int n_parties, uint64_t seed_base,
+                                           int64_t n_instances, uint64_t count, uint32_t flip_q16,
+                                           uint8_t *lists_dev, uint64_t ld, uint64_t inst_stride,
+                                           int64_t *H_dev, int64_t *C_dev, int64_t *P_dev, qba_stream stream);
+QBA_API int qba_sample_check_batched_packed_noisy(qba_ctx *ctx, int n_parties, uint64_t seed_base,
+                                                  int64_t n_instances, uint64_t count, uint32_t flip_q16,
+                                                  uint8_t *packed_dev, uint64_t ld, uint64_t inst_stride,
+                                                  int64_t *H_dev, int64_t *C_dev, int64_t *P_dev,
+                                                  qba_stream stream);
+
 /* The protocol rounds of the batched instances, decided on the device from
  * their count tables (H_dev, C_dev, P_dev in the layout of
  * qba_sample_check_batched): replaces, per instance, the dishonest draw

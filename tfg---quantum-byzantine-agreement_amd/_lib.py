@@ -56,6 +56,9 @@ SIGNATURES = {
     "qba_lists_unpack": [_p, _p, _u64, C.c_int, _u64, _p, _u64, _p],
     "qba_sample_check_batched": [_p, C.c_int, _u64, _i64, _u64, _p, _u64, _u64, _p, _p, _p, _p],
     "qba_sample_check_batched_packed": [_p, C.c_int, _u64, _i64, _u64, _p, _u64, _u64, _p, _p, _p, _p],
+    "qba_sample_check_batched_noisy": [_p, C.c_int, _u64, _i64, _u64, C.c_uint32, _p, _u64, _u64, _p, _p, _p, _p],
+    "qba_sample_check_batched_packed_noisy": [_p, C.c_int, _u64, _i64, _u64, C.c_uint32, _p, _u64, _u64, _p, _p, _p,
+                                              _p],
     "qba_protocol_batched": [_p, C.c_int, C.c_int, _u64, _i64, _p, _p, _p, _p, _p],
     "qba_montecarlo_sampled": [_p, C.c_int, C.c_int, _u64, _i64, _u64, _p, _p],
     "qba_montecarlo_lists": [_p, C.c_int, C.c_int, _u64, _i64, _u64, _p, _u64, _u64, _p, _p],

@@ -31,7 +31,8 @@ struct QbaBatch {
   uint64_t ld, inst_stride;
   int64_t *H, *C, *P;
   hipStream_t stream;
-  int packed;  // nibble rows: ld / inst_stride in bytes of packed rows
+  int packed;      // nibble rows: ld / inst_stride in bytes of packed rows
+  QbaNoise noise;  // read by the noisy kernels alone (qba_sample_check_batched*_noisy with flip_q16 > 0)
 };
 
 // qba_montecarlo_sampled and qba_montecarlo_curve_sampled (qba_mc_kern.h);
@@ -58,6 +59,9 @@ int qba_launch_lists(qba_ctx *ctx, const QbaLaunch &L);
 int qba_flush_pending(qba_ctx *ctx, hipStream_t next);
 template <int NP>
 int qba_launch_batched(qba_ctx *ctx, const QbaBatch &B);
+// the same through the noisy kernels (qba_lists_noise_inst.hip)
+template <int NP>
+int qba_launch_batched_noisy(qba_ctx *ctx, const QbaBatch &B);
 template <int NP>
 int qba_launch_mc(qba_ctx *ctx, const QbaMc &M);
 // the same through the noisy kernels (qba_mc_noise_inst.hip)

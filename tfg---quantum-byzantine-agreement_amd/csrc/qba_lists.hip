@@ -61,9 +61,15 @@ static int with_n(int n, const F &f) {
   }
 }
 
-static int batched(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst, uint64_t count, uint8_t *lists,
-                   uint64_t ld, uint64_t inst_stride, int64_t *H, int64_t *C, int64_t *P, qba_stream stream,
-                   bool packed, const char *who) {
+static const char *bad_flip(uint32_t flip_q16) { return flip_q16 > 65535u ? "flip_q16 must be <= 65535" : nullptr; }
+
+// The four batched calls: byte or nibble rows, noiseless (flip_q16 0: the
+// noiseless kernel) or noisy.  flip_q16 is checked before ctx is looked at,
+// as in the noisy Monte-Carlo calls.
+static int batched(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst, uint64_t count, uint32_t flip_q16,
+                   uint8_t *lists, uint64_t ld, uint64_t inst_stride, int64_t *H, int64_t *C, int64_t *P,
+                   qba_stream stream, bool packed, const char *who) {
+  if (const char *bad = bad_flip(flip_q16)) return qba_fail(QBA_EINVAL, std::string(who) + ": " + bad);
   int rc = check_common(ctx, n, lists, count, ld, who, packed);
   if (rc) return rc;
   if (n_inst < 0 || !H || !C || !P || (n_inst > 1 && inst_stride < (uint64_t)(n + 1) * ld) ||
@@ -73,22 +79,41 @@ static int batched(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst, uint
   if (n_inst == 0 || count == 0) return QBA_OK;
   if ((rc = need_program(ctx, n, who))) return rc;
   QbaBatch B{n, (const QbaProgramSet *)ctx->prog_dev[n], seed_base, n_inst, count, lists, ld,
-             inst_stride, H, C, P, (hipStream_t)stream, packed ? 1 : 0};
+             inst_stride, H, C, P, (hipStream_t)stream, packed ? 1 : 0, {}};
+  if (flip_q16) {
+    B.noise = qba_noise_of(flip_q16);
+    return with_n(n, [&](auto k) { return qba_launch_batched_noisy<decltype(k)::value>(ctx, B); });
+  }
   return with_n(n, [&](auto k) { return qba_launch_batched<decltype(k)::value>(ctx, B); });
 }
 
 extern "C" int qba_sample_check_batched(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst, uint64_t count,
                                         uint8_t *lists, uint64_t ld, uint64_t inst_stride, int64_t *H, int64_t *C,
                                         int64_t *P, qba_stream stream) {
-  return batched(ctx, n, seed_base, n_inst, count, lists, ld, inst_stride, H, C, P, stream, false,
+  return batched(ctx, n, seed_base, n_inst, count, 0u, lists, ld, inst_stride, H, C, P, stream, false,
                  "qba_sample_check_batched");
+}
+
+extern "C" int qba_sample_check_batched_noisy(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst, uint64_t count,
+                                              uint32_t flip_q16, uint8_t *lists, uint64_t ld, uint64_t inst_stride,
+                                              int64_t *H, int64_t *C, int64_t *P, qba_stream stream) {
+  return batched(ctx, n, seed_base, n_inst, count, flip_q16, lists, ld, inst_stride, H, C, P, stream, false,
+                 "qba_sample_check_batched_noisy");
 }
 
 extern "C" int qba_sample_check_batched_packed(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst, uint64_t count,
                                                uint8_t *packed, uint64_t ld, uint64_t inst_stride, int64_t *H,
                                                int64_t *C, int64_t *P, qba_stream stream) {
-  return batched(ctx, n, seed_base, n_inst, count, packed, ld, inst_stride, H, C, P, stream, true,
+  return batched(ctx, n, seed_base, n_inst, count, 0u, packed, ld, inst_stride, H, C, P, stream, true,
                  "qba_sample_check_batched_packed");
+}
+
+extern "C" int qba_sample_check_batched_packed_noisy(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst,
+                                                     uint64_t count, uint32_t flip_q16, uint8_t *packed, uint64_t ld,
+                                                     uint64_t inst_stride, int64_t *H, int64_t *C, int64_t *P,
+                                                     qba_stream stream) {
+  return batched(ctx, n, seed_base, n_inst, count, flip_q16, packed, ld, inst_stride, H, C, P, stream, true,
+                 "qba_sample_check_batched_packed_noisy");
 }
 
 // The two sampled calls behind their envelopes: M holds the checkpoints
@@ -104,8 +129,6 @@ static int mc_sampled(qba_ctx *ctx, int n, QbaMc &M) {
 
 // The single-count and the curve call, noiseless (flip_q16 0: the noiseless
 // kernel) or noisy, behind the names they are exported under.
-static const char *bad_flip(uint32_t flip_q16) { return flip_q16 > 65535u ? "flip_q16 must be <= 65535" : nullptr; }
-
 static int mc_one(const char *who, qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst, uint64_t count,
                   uint32_t flip_q16, int32_t *out, qba_stream stream) {
   QbaMc M{who, nullptr, seed_base, n_inst, n_dis, out, (hipStream_t)stream, {{(uint32_t)count}, 1}, 0, {}};

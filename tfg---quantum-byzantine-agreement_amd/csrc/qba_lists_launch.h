@@ -113,10 +113,25 @@ struct QbaKPbDef {
   template <int QPT, int PK>
   static const void *at() { return (const void *)qba_k_lists_pbdef<NP, QPT, PK>; }
 };
+// NOISE: the family's kernels take B.noise after the common arguments
 template <int NP, int S>
 struct QbaKBatched {
+  static constexpr bool NOISE = false;
   template <int QPT, int PK>
   static const void *at() { return (const void *)qba_k_batched<NP, S, QPT, PK>; }
+};
+// No one-quad kernel on nibble rows: the batched calls refuse rows that are
+// not 4-byte aligned, which is all rows_wide asks of nibble rows, so that step
+// shape is never picked (qba_k_batched<NP, S, 1, 1> is as unreachable; it stays,
+// being part of the code objects that must not change).
+template <int NP, int S>
+struct QbaKBatchedNoisy {
+  static constexpr bool NOISE = true;
+  template <int QPT, int PK>
+  static const void *at() {
+    if constexpr (QPT == 1 && PK == 1) return nullptr;
+    else return (const void *)qba_k_batched_noisy<NP, S, QPT, PK>;
+  }
 };
 
 // The kernel of a synchronous launch; null: a closed-form program beyond n = 11.
@@ -360,8 +375,10 @@ int qba_launch_lists(qba_ctx *ctx, const QbaLaunch &L) {
   return launch_sync<NP>(ctx, L, P.sync);
 }
 
-template <int NP>
-int qba_launch_batched(qba_ctx *ctx, const QbaBatch &B) {
+// The batched launch of kernel family F: qba_k_batched, or qba_k_batched_noisy,
+// which takes B.noise after the same arguments and runs in the same shape.
+template <int NP, template <int, int> class F>
+static int launch_batched(qba_ctx *ctx, const QbaBatch &B) {
   const QbaProgramSet *hs = reinterpret_cast<const QbaProgramSet *>(ctx->prog_host[NP]);
   const int samp = sampler_of<NP>(hs);
   if (int rc = check_closed<NP>(hs)) return rc;
@@ -370,12 +387,31 @@ int qba_launch_batched(qba_ctx *ctx, const QbaBatch &B) {
   const bool wide = rows_wide(B.packed, B.lists, B.ld, B.inst_stride);
   const int64_t cap = (int64_t)ctx->num_cus * 16;
   const int grid = (int)(B.n_inst < cap ? B.n_inst : cap);
-  const void *kern = pick_sampler<NP, QbaKBatched>(samp, B.packed, wide);
-  if (!kern) return qba_fail(QBA_EUNSUPPORTED, "closed form beyond n = 11");
+  if (samp == QBA_S_CLOSED && NP > QBA_CLOSED_MAX_N) return qba_fail(QBA_EUNSUPPORTED, "closed form beyond n = 11");
+  const void *kern = pick_sampler<NP, F>(samp, B.packed, wide);
+  if (!kern) return qba_fail(QBA_EINVAL, "nibble rows must be 4-byte aligned");  // refused before (qba_lists.hip)
   if (int rc = lds_allow(kern, lds)) return rc;
   // (B's fields have the kernel arguments' types)
-  const void *args[] = {&B.ps, &B.seed_base, &B.n_inst, &B.count, &B.lists, &B.ld, &B.inst_stride, &B.H, &B.C, &B.P};
-  QBA_HIP(hipLaunchKernel(kern, dim3(grid), dim3(QBA_BLOCK), const_cast<void **>(args), lds, B.stream));
+  constexpr int NARGS = 10 + (F<NP, QBA_S_GENERAL>::NOISE ? 1 : 0);
+  const void *all[] = {&B.ps, &B.seed_base, &B.n_inst, &B.count, &B.lists, &B.ld, &B.inst_stride, &B.H, &B.C, &B.P,
+                       &B.noise};
+  void *args[NARGS];
+  for (int i = 0; i < NARGS; ++i) args[i] = const_cast<void *>(all[i]);
+  QBA_HIP(hipLaunchKernel(kern, dim3(grid), dim3(QBA_BLOCK), args, lds, B.stream));
   QBA_HIP(hipGetLastError());
   return QBA_OK;
 }
+
+// The noiseless kernels are instantiated by qba_lists_inst.hip, the noisy ones
+// by qba_lists_noise_inst.hip: code objects of their own (as qba_mc_kern.h).
+#ifndef QBA_BATCHED_NOISY_INST
+template <int NP>
+int qba_launch_batched(qba_ctx *ctx, const QbaBatch &B) {
+  return launch_batched<NP, QbaKBatched>(ctx, B);
+}
+#else
+template <int NP>
+int qba_launch_batched_noisy(qba_ctx *ctx, const QbaBatch &B) {
+  return launch_batched<NP, QbaKBatchedNoisy>(ctx, B);
+}
+#endif

@@ -4,6 +4,7 @@
 // and counts with qba_lists_count.h (the queue, qba_count_quad, qba_pb_flush).
 #pragma once
 #include "qba_lists_count.h"
+#include "qba_noise.h"
 
 // 4x4 byte transpose: r_i byte j = input j byte i (an involution).
 __device__ __forceinline__ void qba_t4(uint32_t a, uint32_t b, uint32_t c, uint32_t d, uint32_t &r0,
@@ -16,21 +17,43 @@ __device__ __forceinline__ void qba_t4(uint32_t a, uint32_t b, uint32_t c, uint3
   r3 = qba_perm_b(t3, t1, 0x07060302u);
 }
 
+// The qubit-flip noise of a sampled quad (qba_noise.h; the noisy batched
+// kernels): entry c0 + j of the instance keyed (k0, k1) takes its mask before
+// anything looks at it.  The entries past `valid` of a partial quad stay 0.
+template <int NP>
+__device__ __forceinline__ void qba_noise_quad(uint32_t c0, int valid, uint32_t k0, uint32_t k1, const QbaNoise &nz,
+                                               uint32_t (&D)[4][CF<NP>::ND]) {
+  using C = QCfg<NP>;
+  constexpr int ND = CF<NP>::ND;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (j >= valid) continue;
+    uint32_t T[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < ND; ++i) T[i] = D[j][i];
+    qba_noise_d<C::G, C::W>(qba_noise_r(c0 + (uint32_t)j, 0u, k0, k1, nz), T);
+#pragma unroll
+    for (int i = 0; i < ND; ++i) D[j][i] = T[i];
+  }
+}
+
 // One thread-step over QPT consecutive quads: entries [c0, c0 + 4 QPT) of the
 // launch (columns of `lists`).  Each list row is stored / loaded as one
 // 4*QPT-byte vector per thread (16 B at QPT = 4: a wave moves 1 KiB per row).
 // MODE 0: sample -> lists;  MODE 1: sample -> lists + counts;  MODE 2: lists -> counts
 // TAIL (QPT = 1 only): the last, partial quad, byte by byte.
-template <int NP, int MODE, int SAMP, int QPT, bool TAIL, bool WQ = false, int CNT = 0, int PW = QBA_PAIRWISE>
+template <int NP, int MODE, int SAMP, int QPT, bool TAIL, bool WQ = false, int CNT = 0, int PW = QBA_PAIRWISE,
+          bool NZ = false>
 __device__ __forceinline__ void qba_step(uint32_t c0, uint32_t count, uint64_t first, uint32_t k0,
                                          uint32_t k1, const QbaProgramSet *__restrict__ ps,
                                          const uint64_t *pat, const uint64_t *apat,
                                          const uint64_t *thr, const uint32_t *pl,
                                          uint8_t *__restrict__ lists, uint64_t ld, uint32_t *hist,
-                                         QbaWaveQ *wq = nullptr, bool act = true) {
+                                         QbaWaveQ *wq = nullptr, bool act = true, QbaNoise nz = QbaNoise{}) {
   using C = QCfg<NP>;
   constexpr int ND = CF<NP>::ND;
   static_assert(QPT == 1 || QPT == 2 || QPT == 4, "QPT");
+  static_assert(!NZ || (MODE == 1 && CNT == 0), "noise: the batched kernels' sample + check only");
   static_assert(!TAIL || QPT == 1, "tail quads are single");
   static_assert(CNT == 0 || MODE == 1, "pair bins count the fused kernel's own lists only");
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -74,6 +97,7 @@ __device__ __forceinline__ void qba_step(uint32_t c0, uint32_t count, uint64_t f
 #pragma unroll
     for (int k = 0; k < QPT; ++k) {
       qba_sample_quad<NP, SAMP, TAIL, PW>(c0 + 4 * k, valid, first, k0, k1, ps, pat, apat, thr, pl, D);
+      if constexpr (NZ) qba_noise_quad<NP>(c0 + 4 * k, valid, k0, k1, nz, D);
 #pragma unroll
       for (int i = 0; i < ND; ++i)
         qba_t4(D[0][i], D[1][i], D[2][i], D[3][i], row[k][4 * i], row[k][4 * i + 1],
@@ -133,16 +157,18 @@ __device__ __forceinline__ void qba_step(uint32_t c0, uint32_t count, uint64_t f
 // QPT = 1 (unaligned starts, the tail quads): 2 bytes per row, stored as bytes
 // (a chunk may start at an odd byte).  MODE 2 reads the same layout; an
 // unpacked quad's entries come out permuted (counting is order-free).
-template <int NP, int MODE, int SAMP, int QPT, bool TAIL, bool WQ = false, int CNT = 0, int PW = QBA_PAIRWISE>
+template <int NP, int MODE, int SAMP, int QPT, bool TAIL, bool WQ = false, int CNT = 0, int PW = QBA_PAIRWISE,
+          bool NZ = false>
 __device__ __forceinline__ void qba_step_pk(uint32_t c0, uint32_t count, uint64_t first, uint32_t k0,
                                             uint32_t k1, const QbaProgramSet *__restrict__ ps,
                                             const uint64_t *pat, const uint64_t *apat,
                                             const uint64_t *thr, const uint32_t *pl,
                                             uint8_t *__restrict__ lists, uint64_t ld, uint32_t *hist,
-                                            QbaWaveQ *wq, bool act) {
+                                            QbaWaveQ *wq, bool act, QbaNoise nz = QbaNoise{}) {
   using C = QCfg<NP>;
   constexpr int ND = CF<NP>::ND;
   static_assert(QPT == 1 || QPT == 2, "packed rows: QPT 1 or 2");
+  static_assert(!NZ || (MODE == 1 && CNT == 0), "noise: the batched kernels' sample + check only");
   static_assert(!TAIL || QPT == 1, "tail quads are single");
   static_assert(CNT == 0 || MODE != 0, "pair bins count");
   static_assert(C::W <= 16, "a value must fit a nibble");
@@ -201,6 +227,7 @@ __device__ __forceinline__ void qba_step_pk(uint32_t c0, uint32_t count, uint64_
 #pragma unroll
     for (int k = 0; k < QPT; ++k) {
       qba_sample_quad<NP, SAMP, TAIL, PW>(c0 + 4 * k, valid, first, k0, k1, ps, pat, apat, thr, pl, D);
+      if constexpr (NZ) qba_noise_quad<NP>(c0 + 4 * k, valid, k0, k1, nz, D);
 #pragma unroll
       for (int i = 0; i < ND; ++i) {
         Dp[2 * k][i] = D[0][i] | (D[1][i] << 4);
@@ -282,30 +309,34 @@ __device__ __forceinline__ void qba_step_pk(uint32_t c0, uint32_t count, uint64_
   }
 }
 
-template <int NP, int MODE, int SAMP, int QPT, bool TAIL, int PK, bool WQ = false, int CNT = 0, int PW = QBA_PAIRWISE>
+template <int NP, int MODE, int SAMP, int QPT, bool TAIL, int PK, bool WQ = false, int CNT = 0, int PW = QBA_PAIRWISE,
+          bool NZ = false>
 __device__ __forceinline__ void qba_step_l(uint32_t c0, uint32_t count, uint64_t first, uint32_t k0,
                                            uint32_t k1, const QbaProgramSet *__restrict__ ps,
                                            const uint64_t *pat, const uint64_t *apat,
                                            const uint64_t *thr, const uint32_t *pl,
                                            uint8_t *__restrict__ lists, uint64_t ld, uint32_t *hist,
-                                           QbaWaveQ *wq = nullptr, bool act = true) {
+                                           QbaWaveQ *wq = nullptr, bool act = true, QbaNoise nz = QbaNoise{}) {
   if constexpr (PK)
-    qba_step_pk<NP, MODE, SAMP, QPT, TAIL, WQ, CNT, PW>(c0, count, first, k0, k1, ps, pat, apat, thr, pl, lists, ld, hist, wq, act);
+    qba_step_pk<NP, MODE, SAMP, QPT, TAIL, WQ, CNT, PW, NZ>(c0, count, first, k0, k1, ps, pat, apat, thr, pl, lists, ld, hist, wq, act, nz);
   else
-    qba_step<NP, MODE, SAMP, QPT, TAIL, WQ, CNT, PW>(c0, count, first, k0, k1, ps, pat, apat, thr, pl, lists, ld, hist, wq, act);
+    qba_step<NP, MODE, SAMP, QPT, TAIL, WQ, CNT, PW, NZ>(c0, count, first, k0, k1, ps, pat, apat, thr, pl, lists, ld, hist, wq, act, nz);
 }
 
 // One of the quads that remain after a launch's whole thread-steps (< 4 QPT
 // entries, a quad per thread): a whole quad, or the call's last, partial one.
-template <int NP, int MODE, int SAMP, int PK, int CNT = 0, int PW = QBA_PAIRWISE>
+template <int NP, int MODE, int SAMP, int PK, int CNT = 0, int PW = QBA_PAIRWISE, bool NZ = false>
 __device__ __forceinline__ void qba_leftover(uint32_t c0, uint32_t count, uint64_t first, uint32_t k0, uint32_t k1,
                                              const QbaProgramSet *__restrict__ ps, const uint64_t *pat,
                                              const uint64_t *apat, const uint64_t *thr, const uint32_t *pl,
-                                             uint8_t *__restrict__ lists, uint64_t ld, uint32_t *hist) {
+                                             uint8_t *__restrict__ lists, uint64_t ld, uint32_t *hist,
+                                             QbaNoise nz = QbaNoise{}) {
   if (c0 + 4 <= count)
-    qba_step_l<NP, MODE, SAMP, 1, false, PK, false, CNT, PW>(c0, count, first, k0, k1, ps, pat, apat, thr, pl, lists, ld, hist);
+    qba_step_l<NP, MODE, SAMP, 1, false, PK, false, CNT, PW, NZ>(c0, count, first, k0, k1, ps, pat, apat, thr, pl, lists, ld, hist,
+                                                                 nullptr, true, nz);
   else
-    qba_step_l<NP, MODE, SAMP, 1, true, PK, false, CNT, PW>(c0, count, first, k0, k1, ps, pat, apat, thr, pl, lists, ld, hist);
+    qba_step_l<NP, MODE, SAMP, 1, true, PK, false, CNT, PW, NZ>(c0, count, first, k0, k1, ps, pat, apat, thr, pl, lists, ld, hist,
+                                                                nullptr, true, nz);
 }
 
 // The outputs of a counting launch start at zero unless the call accumulates:
@@ -687,6 +718,80 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(1, QBA_BLOCK),
     const uint32_t r0 = nunits * (4 * QPT), rq = ((uint32_t)count - r0 + 3) >> 2;
     if ((uint32_t)tid < rq)
       qba_leftover<NP, 1, SAMP, PK>(r0 + 4 * (uint32_t)tid, (uint32_t)count, 0, k0, k1, ps, pat, apat, thr, pl, L, ld, hist);
+    __syncthreads();
+    int64_t *h = H + inst * C::HB, *c = Cc + inst * C::CB, *p = P + inst * C::W;
+    for (int i = tid; i < C::HB; i += QBA_BLOCK) h[i] = qba_hval<NP>(hist, i);
+    for (int r = tid; r < C::CB; r += QBA_BLOCK) {
+      const int u = r / (C::G * C::G), g = (r / C::G) % C::G, k = r % C::G;
+      const int64_t v = g < k ? hist[C::HBL + u * C::CP + C::pidx(g, k)]
+                              : g > k ? hist[C::HBL + u * C::CP + C::pidx(k, g)]
+                                      : qba_psize<NP>(hist, u);
+      c[r] = v;
+    }
+    for (int u = tid; u < C::W; u += QBA_BLOCK) p[u] = qba_psize<NP>(hist, u);
+    __syncthreads();
+  }
+}
+
+// Waves per SIMD the noisy closed-form batched kernel is compiled for.  The
+// flips are 64 more live bits per entry: up to n = 7 (two words per entry) the
+// step still fits the 64 VGPRs of 8 waves, from n = 8 (three words) it spills
+// at 8 and at 7 waves and is built for 6 (80 VGPRs, no scratch): DESIGN.md
+// section 13.6.
+#ifndef QBA_BATCHED_NOISY_WAVES_SMALL
+#define QBA_BATCHED_NOISY_WAVES_SMALL 8  // an A/B build asks for 6
+#endif
+template <int NP>
+constexpr int qba_batched_noisy_waves() {
+  return CF<NP>::ND <= 2 ? QBA_BATCHED_NOISY_WAVES_SMALL : 6;
+}
+
+// qba_k_batched under qubit-flip noise (qba_sample_check_batched_noisy,
+// DESIGN.md section 13.6): entry e of instance `inst` takes the mask
+// qba_noise_r(e, 0, key of inst) right after it is sampled (the NZ flag of the
+// thread-steps), so the rows stored and the tables counted are those of the
+// noisy entries.  Noise takes no LDS: launch shape, LDS and grid are
+// qba_k_batched's.  A text of its own, instantiated by
+// qba_lists_noise_inst.hip into code objects of its own: one body shared with
+// qba_k_batched changed the code of the closed-form noiseless kernels.
+template <int NP, int SAMP, int QPT, int PK>
+__global__ void __attribute__((amdgpu_flat_work_group_size(1, QBA_BLOCK),
+                               amdgpu_waves_per_eu(SAMP == QBA_S_CLOSED ? qba_batched_noisy_waves<NP>() : 1)))
+    qba_k_batched_noisy(const QbaProgramSet *__restrict__ ps, uint64_t seed_base, int64_t n_inst,
+                        uint64_t count, uint8_t *__restrict__ lists, uint64_t ld, uint64_t inst_stride,
+                        int64_t *__restrict__ H, int64_t *__restrict__ Cc, int64_t *__restrict__ P, QbaNoise nz) {
+  using C = QCfg<NP>;
+  extern __shared__ __align__(16) uint64_t lds[];
+  const uint64_t *pat, *apat, *thr;
+  const uint32_t *pl;
+  uint32_t *hist = qba_stage<NP, 1, SAMP, QBA_BLOCK>(ps, lds, pat, apat, thr, pl);
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int64_t inst = blockIdx.x; inst < n_inst; inst += gridDim.x) {
+    for (int i = (int)((wv << 6) | __lane_id()); i < C::NBINS; i += QBA_BLOCK) hist[i] = 0u;
+    __syncthreads();
+    const uint64_t key = seed_base + (uint64_t)inst;
+    const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
+    uint8_t *L = lists + (uint64_t)inst * inst_stride;
+    const uint32_t nunits = (uint32_t)count / (4 * QPT);
+    QbaWaveQ wq;
+    wq.base = qba_queue_base<NP>(hist) + wv * (CF<NP>::ND * QBA_QCAP * 4);
+    wq.tail = 0;
+    wq.qn = 0;
+    wq.hoff = (uint32_t)(uintptr_t)(qba_lds_u32 *)hist;
+    asm("" : "+v"(wq.hoff));
+    for (uint32_t u = (wv << 6) | __lane_id();; u += QBA_BLOCK) {  // wave-uniform trip count
+      const bool act = u < nunits;
+      if (!__any(act)) break;
+      qba_step_l<NP, 1, SAMP, QPT, false, PK, true, 0, QBA_PAIRWISE, true>(u * (4 * QPT), (uint32_t)count, 0, k0, k1, ps, pat,
+                                                                           apat, thr, pl, L, ld, hist, &wq, act, nz);
+    }
+    while (wq.qn) qba_q_drain<NP, true>(wq, hist, wq.qn < 64 ? wq.qn : 64u);  // wave-uniform
+    int tid = (int)((wv << 6) | __lane_id());
+    asm volatile("" : "+v"(tid));  // opaque: the addresses built from it are not hoisted out of the instance loop
+    const uint32_t r0 = nunits * (4 * QPT), rq = ((uint32_t)count - r0 + 3) >> 2;
+    if ((uint32_t)tid < rq)
+      qba_leftover<NP, 1, SAMP, PK, 0, QBA_PAIRWISE, true>(r0 + 4 * (uint32_t)tid, (uint32_t)count, 0, k0, k1, ps, pat, apat,
+                                                           thr, pl, L, ld, hist, nz);
     __syncthreads();
     int64_t *h = H + inst * C::HB, *c = Cc + inst * C::CB, *p = P + inst * C::W;
     for (int i = tid; i < C::HB; i += QBA_BLOCK) h[i] = qba_hval<NP>(hist, i);

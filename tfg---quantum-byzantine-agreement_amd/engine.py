@@ -263,10 +263,14 @@ class Engine:
 
     def sample_check_batched(self, n: int, seed_base: int, n_inst: int, count: int,
                              lists: Optional[torch.Tensor] = None,
-                             packed: bool = False) -> Tuple[torch.Tensor, Counts]:
+                             packed: bool = False, flip_q16: int = 0) -> Tuple[torch.Tensor, Counts]:
         """n_inst independent runs (key seed_base + i) of `count` entries each.
         Returns lists [n_inst, n+1, ld] (nibble rows when packed) and
-        per-instance counts [n_inst, ...]."""
+        per-instance counts [n_inst, ...].  ``flip_q16=k > 0``
+        (qba_sample_check_batched_noisy / _packed_noisy): every measured bit of
+        an entry flips with probability k / 65536 (montecarlo.noise_masks) as
+        it is sampled; the lists and the counts are those of the noisy entries."""
+        flip = self._check_flip(flip_q16)
         self.prepare(n)
         _, w = self.sizes(n)
         nb = (count + 1) // 2 if packed else count
@@ -278,10 +282,13 @@ class Engine:
         counts = Counts(z(n_inst, w, n + 1, w), z(n_inst, w, n + 1, n + 1), z(n_inst, w))
         if lists.shape[2] < nb:
             raise QbaError("lists rows too short for `count` entries")
-        call("qba_sample_check_batched_packed" if packed else "qba_sample_check_batched", self.ctx, n,
-             seed_base, n_inst, count, _ptr(lists),
-             lists.stride(1), lists.stride(0), _ptr(counts.H), _ptr(counts.C), _ptr(counts.P),
-             self.stream())
+        name = "qba_sample_check_batched_packed" if packed else "qba_sample_check_batched"
+        rest = (_ptr(lists), lists.stride(1), lists.stride(0), _ptr(counts.H), _ptr(counts.C), _ptr(counts.P),
+                self.stream())
+        if flip:
+            call(name + "_noisy", self.ctx, n, _u64(seed_base), n_inst, count, flip, *rest)
+        else:  # (ctypes reduces the seed mod 2^64 as _u64 does)
+            call(name, self.ctx, n, _u64(seed_base), n_inst, count, *rest)
         return lists, counts
 
     def protocol_batched(self, n: int, n_dishonest: int, seed_base: int, counts: Counts,

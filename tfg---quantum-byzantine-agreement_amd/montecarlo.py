@@ -33,11 +33,14 @@ pass: the lists at sizeL = c are the first c columns of the lists at any larger
 sizeL, and those reductions are monotone.  :func:`curve_host` is its
 specification.
 
-Qubit-flip noise (``flip_q16=k`` on the calls below):
-every measured bit of an entry flips independently with probability k / 65536
-before anything looks at the entry.  :func:`noise_masks` is the definition;
-the fused kernels draw the same flips inside (``Engine.montecarlo_sampled(...,
-flip_q16=k)``), and ``Engine.noise_apply`` XORs them into device lists.
+Qubit-flip noise (``flip_q16=k`` on the calls below; DESIGN.md sections 13.5
+and 13.6): every measured bit of an entry flips independently with probability
+k / 65536 before anything looks at the entry.  :func:`noise_masks` is the
+definition; the fused kernels draw the same flips inside
+(``Engine.montecarlo_sampled(..., flip_q16=k)``), so does the batched sampler
+(``Engine.sample_check_batched(..., flip_q16=k)``, ``run(path="tables_noisy")``:
+the noisy lists and their count tables stay on the device for the caller), and
+``Engine.noise_apply`` XORs them into device lists.
 """
 from __future__ import annotations
 
@@ -470,13 +473,16 @@ def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, pack
     indices of up to F runs without success (run i has key ``seed + i``), and
     ``failed_total``, how many there were.
 
-    ``flip_q16=k > 0`` (``path="fused"`` only; the tables path has no noisy
-    sampler): every measured bit flips with probability k / 65536."""
-    if path not in ("tables", "fused"):
-        raise ValueError("path is 'tables' or 'fused'")
+    ``flip_q16=k > 0`` (``path="fused"`` or ``path="tables_noisy"``): every
+    measured bit flips with probability k / 65536.  ``"tables_noisy"`` is the
+    tables path through the noisy batched sampler
+    (``sample_check_batched(..., flip_q16=k)``): the same rows as ``"fused"``;
+    with ``flip_q16=0`` it is ``"tables"``."""
+    if path not in ("tables", "fused", "tables_noisy"):
+        raise ValueError("path is 'tables', 'fused' or 'tables_noisy'")
     noise = {"flip_q16": _check_flip(flip_q16)} if flip_q16 else {}
     if noise and path == "tables":
-        raise ValueError("flip_q16 > 0 needs path='fused': the tables path has no noisy sampler")
+        raise ValueError("flip_q16 > 0 needs path='fused' or path='tables_noisy'")
     lists = None
 
     def decide(key, b, out=None):
@@ -485,7 +491,7 @@ def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, pack
         if path == "fused":
             return engine.montecarlo_sampled(n, n_dishonest, key, b, sizeL, **into, **noise)
         buf, counts = engine.sample_check_batched(n, key, b, sizeL, None if lists is None else lists[:b],
-                                                  packed=packed)
+                                                  packed=packed, **noise)
         if lists is None:
             lists = buf
         return engine.protocol_batched(n, n_dishonest, key, counts, **into)

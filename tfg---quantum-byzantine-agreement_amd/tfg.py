@@ -77,8 +77,12 @@ def _args(argv):
                          "replay under key seed + index; implies --tally")
     ap.add_argument("--flip", type=int, default=None, metavar="K",
                     help="with --runs: every measured qubit flips with probability K / 65536, 0 <= K <= 65535 "
-                         "(montecarlo.noise_masks); implies --fused; with K > 0 the summary lines end in "
-                         "flip=K/65536")
+                         "(montecarlo.noise_masks); implies --fused unless --tables is given; with K > 0 the "
+                         "summary lines end in flip=K/65536")
+    ap.add_argument("--tables", action="store_true",
+                    help="with --runs: sample and count each batch's lists in the batched sampler, then decide them "
+                         "(montecarlo.run path='tables_noisy'): with --flip K the noisy lists and tables, the same "
+                         "instances and summary as the fused kernels'; not with --curve or --fused")
     ap.add_argument("--quiet", action="store_true", help="print only the outcome")
     ap.add_argument("--timing", action="store_true", help="print the wall time of the run")
     ap.add_argument("--wire", action="store_true",
@@ -97,12 +101,17 @@ def _args(argv):
         ap.error("--failures: K >= 0")
     if (a.tally or a.failures) and a.runs is None:
         ap.error("--tally and --failures need --runs")
+    if a.tables:
+        if a.runs is None:
+            ap.error("--tables needs --runs")
+        if a.curve is not None or a.fused:
+            ap.error("--tables: not with --curve or --fused")
     if a.flip is not None:
         if a.runs is None:
             ap.error("--flip needs --runs")
         if not 0 <= a.flip <= 65535:
             ap.error("--flip: K must be in [0, 65535] (out of 65536)")
-        a.fused = True
+        a.fused = not a.tables
     return a
 
 
@@ -230,7 +239,8 @@ def _montecarlo(a, eng, size_l) -> int:
         points = montecarlo.curve(a.parties, a.curve, a.nDishonest, a.runs, seed, eng, batch=a.batch, **how)
     else:
         points = {size_l: montecarlo.run(a.parties, size_l, a.nDishonest, a.runs, seed, eng, batch=a.batch,
-                                         path="fused" if a.fused else "tables", **how)}
+                                         path="tables_noisy" if a.tables else "fused" if a.fused else "tables",
+                                         **how)}
     for c, s in points.items():
         print(f"Runs: {s['runs']} Successes: {s['successes']} Rate: {s['rate']:.6f} "
               f"(n={a.parties}, sizeL={c}, dishonest={a.nDishonest}, empty-V_i runs={s['empty_vi_runs']}){noise}")

@@ -31,6 +31,13 @@ instances x n = 7 x sizeL = 1e5, 2 dishonest, on one GPU.
       point and runs the noiseless kernel.  Reports noisy / noiseless at the
       medians and the Philox blocks per entry the noise adds.
 
+  --flip K --tables  (per --sizeL and K) the noisy tables path beside the noisy
+      fused call at the same shape, in one session: the noisy batched call
+      (qba_sample_check_batched_packed_noisy, nibble rows), that call followed
+      by protocol_batched as one interval, and qba_montecarlo_sampled_noisy.
+      The rows of the two routes are compared; a route is called faster only
+      where the min-max ranges are apart.
+
 (a), (b), (d), the --tally calls, the --flip calls and the --curve pair are device-event times of single calls on warm code: median, min
 and max over --repeats launches after --warmup launches.  (c) is host wall
 time around runs that end in device synchronisation (each reads its tables
@@ -84,10 +91,18 @@ def main(argv=None) -> int:
     ap.add_argument("--flip", type=int, action="append", default=None, metavar="K",
                     help="time the noisy fused call (with --curve: the noisy curve call) at flip probability "
                          "K / 65536 beside the noiseless one; repeatable; nothing else is measured")
+    ap.add_argument("--tables", action="store_true",
+                    help="with --flip: time the noisy batched call, the same followed by protocol_batched, and the "
+                         "noisy fused call at each --sizeL and K, and compare their rows")
     a = ap.parse_args(argv)
+    if a.tables and (not a.flip or a.curve or a.tally):
+        ap.error("--tables needs --flip and goes with neither --curve nor --tally")
 
     eng = importlib.import_module(f"{PKG}.engine").Engine(0)
-    if a.flip:
+    if a.tables:
+        lines = [json.dumps(_measure_flip_tables(a, eng, size_l, k)) for size_l in (a.sizeL or [100_000])
+                 for k in a.flip]
+    elif a.flip:
         shapes = ([sorted({int(c) for c in text.split(",")}) for text in a.curve] if a.curve
                   else [[s] for s in (a.sizeL or [100_000])])
         lines = [json.dumps(_measure_flip(a, eng, counts, bool(a.curve))) for counts in shapes]
@@ -176,6 +191,38 @@ def _measure_flip(a, eng, counts, curve: bool) -> dict:
     res["noiseless_spread_at_median"] = abs(res["noiseless"]["median_ms"] - res["noiseless_again"]["median_ms"]) / base
     for t in res["flips"].values():
         t["over_noiseless_at_median"] = t["median_ms"] / base
+    return res
+
+
+def _measure_flip_tables(a, eng, size_l, k) -> dict:
+    """--flip K --tables: the noisy tables path against the noisy fused call."""
+    import torch
+    n, nd, inst = a.parties, a.dishonest, a.instances
+    lists, counts = eng.sample_check_batched(n, a.seed, inst, size_l, packed=True, flip_q16=k)
+    out = eng.protocol_batched(n, nd, a.seed, counts)
+    fused = eng.montecarlo_sampled(n, nd, a.seed, inst, size_l, flip_q16=k)
+    torch.cuda.synchronize()
+
+    def batched():
+        return eng.sample_check_batched(n, a.seed, inst, size_l, lists, packed=True, flip_q16=k)
+
+    def both():
+        _, c = batched()
+        eng.protocol_batched(n, nd, a.seed, c, out)
+
+    res = {"config": {"n": n, "sizeL": size_l, "dishonest": nd, "instances": inst, "seed": a.seed, "flip_q16": k,
+                      "noise_blocks_per_entry": 0 if k == 0 else (16 - ((k & -k).bit_length() - 1) + 1) // 2,
+                      "device": torch.cuda.get_device_name(0)}}
+    res["noisy_batched"] = _events(batched, a.warmup, a.repeats)
+    res["noisy_batched_plus_protocol"] = _events(both, a.warmup, a.repeats)
+    res["fused_noisy"] = _events(lambda: eng.montecarlo_sampled(n, nd, a.seed, inst, size_l, fused, flip_q16=k),
+                                 a.warmup, a.repeats)
+    res["rows_equal"] = bool(torch.equal(out, fused))
+    t, f = res["noisy_batched_plus_protocol"], res["fused_noisy"]
+    res["fused_over_tables_at_median"] = f["median_ms"] / t["median_ms"]
+    # faster only where the min-max ranges do not overlap
+    res["tables_faster"] = t["max_ms"] < f["min_ms"]
+    res["fused_faster"] = f["max_ms"] < t["min_ms"]
     return res
 
 
