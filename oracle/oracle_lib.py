@@ -139,6 +139,34 @@ def batched_counts(n: int, seed_base: int, n_inst: int, count: int, prog_notq: d
     return H, Cc, P
 
 
+SCAN_KINDS = {"w0": 0, "retry1": 1, "retry_late": 2, "retry64": 3}
+
+
+def scan_rare(n: int, sampler: str, kind: str, key0: int, nkeys: int, e0: int, ne: int, cap: int = 1,
+              h: int = -1) -> list:
+    """The first `cap` positions, keys [key0, key0 + nkeys) outermost and entries
+    [e0, e0 + ne) inside, at which `sampler` ("closed": n <= 11, e0 and ne even;
+    "perm64": the 64-bit permutation of the table samplers) takes the rare
+    branch `kind` (oracle_scan_rare in sampler_ref.c: "w0", "retry1",
+    "retry_late"; "retry64"), on half h of a closed-form pair only when h is 0
+    or 1.  Dicts of key, entry, word (the accepted rank word), where (closed
+    form: 4 * (a - 1) + i for word i of retry block a; retry64: the number of
+    retry blocks) and blocks (first-candidate Philox blocks of the scan up to
+    and including the hit's)."""
+    closed = {"closed": True, "perm64": False}[sampler]
+    out = np.zeros((cap, 4), np.uint64)
+    lib().oracle_scan_rare.restype = C.c_int64
+    got = lib().oracle_scan_rare(C.c_int(n), C.c_int(0 if closed else 1), C.c_int(SCAN_KINDS[kind]), C.c_int(h),
+                                 C.c_uint64(key0), C.c_uint64(nkeys), C.c_uint64(e0), C.c_uint64(ne),
+                                 C.c_int64(cap), _p(out))
+    if got < 0:
+        raise ValueError(f"scan_rare: arguments out of range ({n}, {sampler}, {kind}, h={h}, e0={e0}, ne={ne})")
+    upk, shift = (ne // 2, 1) if closed else (ne, 0)
+    return [{"key": int(k), "entry": int(e), "word": int(w), "where": int(a),
+             "blocks": ((int(k) - key0) % (1 << 64)) * upk + ((int(e) - e0) >> shift) + 1}
+            for k, e, w, a in out[:got].tolist()]
+
+
 def threads() -> int:
     return int(lib().oracle_threads())
 

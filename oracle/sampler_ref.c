@@ -441,6 +441,173 @@ void oracle_stream_row_sums(int n, uint64_t seed, uint64_t first, uint64_t count
   }
 }
 
+/* ---------------- rare-branch scanner ----------------
+ * Positions (key, entry) at which a sampler leaves its common path, for the
+ * directed fixtures of tests/golden/sampler_rare.json.  The classification
+ * reads the Philox words and the thresholds alone, restated here from
+ * csrc/qba_lists_sample.h's header comment: it calls neither closed_entry nor
+ * sample_outcome (nor their helpers), so that the fixture can hold them.
+ *
+ *   sampler 0, closed form (2 <= n <= 11), Q entries (w0 & 1) only; entry e is
+ *   half h = e & 1 of its pair's block, F accepted iff F * n! mod 2^32 >= T:
+ *     kind 0  w0          w1 rejected (T = 2^32 mod n!), w0 & ~31 accepted
+ *                         (T = (2^27 mod n!) << 5)
+ *     kind 1  retry1      both rejected, word 0 of retry block 1 accepted
+ *     kind 2  retry_late  both rejected, word 0 of retry block 1 rejected
+ *   sampler 1, 64-bit permutation (n <= 15), Q entries (x0 & 1) only:
+ *     kind 3  retry64     F = x2 | x3 << 32 rejected (F * n! mod 2^64 <
+ *                         2^64 mod n!)
+ *
+ * Scan order: keys [key0, key0 + nkeys) outermost, entries [e0, e0 + ne) inside
+ * (closed form: e0 and ne even, so that a pair's block is read once); h = 0 / 1
+ * keeps one half only, -1 both.  out[i] = {key, entry, accepted rank word,
+ * where}: where = 4 * (a - 1) + i for word i of closed-form retry block a (0
+ * for kind 0), the number of retry blocks for retry64.  Returns the number of
+ * hits written, the first `cap` in scan order whatever the thread count, or
+ * -1 on arguments out of range. */
+enum { SCAN_W0 = 0, SCAN_RETRY1 = 1, SCAN_RETRY_LATE = 2, SCAN_RETRY64 = 3 };
+
+typedef struct {
+  int n, sampler, kind, want_h;
+  uint64_t key0, e0, upk; /* upk: units (pairs, or entries) per key */
+  uint32_t f32, t32, t27;
+  uint64_t f64, t64;
+} scan_t;
+
+static int scan_closed_half(const scan_t *s, const uint32_t key[2], uint64_t p, uint32_t h, const uint32_t x[4],
+                            uint64_t hit[4]) {
+  const uint32_t w0 = x[2 * h], w1 = x[2 * h + 1];
+  if ((uint32_t)(w1 * s->f32) >= s->t32 || !(w0 & 1u)) return 0;
+  if (s->want_h >= 0 && (uint32_t)s->want_h != h) return 0;
+  const uint32_t second = w0 & ~31u;
+  const int second_ok = (uint32_t)(second * s->f32) >= s->t27;
+  if (s->kind == SCAN_W0) {
+    hit[2] = second;
+    hit[3] = 0;
+    return second_ok;
+  }
+  if (second_ok) return 0;
+  for (uint32_t a = 1;; ++a) {
+    const uint32_t ctr[4] = {(uint32_t)p, (uint32_t)(p >> 32), 0x80000000u + a, h};
+    uint32_t y[4];
+    philox4x32_10(ctr, key, y);
+    for (uint32_t i = 0; i < 4; ++i)
+      if ((uint32_t)(y[i] * s->f32) >= s->t32) {
+        hit[2] = y[i];
+        hit[3] = 4 * (a - 1) + i;
+        return (s->kind == SCAN_RETRY1) == (hit[3] == 0);
+      }
+  }
+}
+
+/* unit u of the scan; appends its hits (at most 2) to hit[][4] */
+static int scan_unit(const scan_t *s, uint64_t k, uint64_t r, uint64_t hit[2][4]) {
+  const uint64_t seed = s->key0 + k;
+  const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+  uint32_t x[4];
+  int got = 0;
+  if (s->sampler == 0) {
+    const uint64_t p = (s->e0 >> 1) + r;
+    const uint32_t ctr[4] = {(uint32_t)p, (uint32_t)(p >> 32), 0u, 0u};
+    philox4x32_10(ctr, key, x);
+    for (uint32_t h = 0; h < 2; ++h)
+      if (scan_closed_half(s, key, p, h, x, hit[got])) {
+        hit[got][0] = seed;
+        hit[got][1] = 2 * p + h;
+        ++got;
+      }
+    return got;
+  }
+  const uint64_t e = s->e0 + r;
+  const uint32_t ctr[4] = {(uint32_t)e, (uint32_t)(e >> 32), 0u, 0u};
+  philox4x32_10(ctr, key, x);
+  uint64_t F = (uint64_t)x[2] | ((uint64_t)x[3] << 32);
+  if (!(x[0] & 1u) || F * s->f64 >= s->t64) return 0;
+  uint32_t a = 0;
+  while (F * s->f64 < s->t64) {
+    const uint32_t c2[4] = {(uint32_t)e, (uint32_t)(e >> 32), 0x80000000u + ++a, 0u};
+    philox4x32_10(c2, key, x);
+    F = (uint64_t)x[0] | ((uint64_t)x[1] << 32);
+  }
+  hit[0][0] = seed;
+  hit[0][1] = e;
+  hit[0][2] = F;
+  hit[0][3] = a;
+  return 1;
+}
+
+int64_t oracle_scan_rare(int n, int sampler, int kind, int want_h, uint64_t key0, uint64_t nkeys, uint64_t e0,
+                         uint64_t ne, int64_t cap, uint64_t *out) {
+  scan_t s = {n, sampler, kind, want_h, key0, e0, 0, 1, 0, 0, 1, 0};
+  if (cap < 1 || want_h < -1 || want_h > 1 || nkeys > ((uint64_t)1 << 40) || ne > ((uint64_t)1 << 40)) return -1;
+  if (sampler == 0) {
+    if (n < 2 || n > 11 || kind < SCAN_W0 || kind > SCAN_RETRY_LATE || (e0 & 1) || (ne & 1)) return -1;
+    for (int i = 2; i <= n; ++i) s.f32 *= (uint32_t)i;
+    s.t32 = (uint32_t)(((uint64_t)1 << 32) % s.f32);
+    s.t27 = (uint32_t)((((uint64_t)1 << 27) % s.f32) << 5);
+    s.upk = ne / 2;
+  } else if (sampler == 1) {
+    if (n < 2 || n > 15 || kind != SCAN_RETRY64 || want_h != -1) return -1;
+    for (int i = 2; i <= n; ++i) s.f64 *= (uint64_t)i;
+    s.t64 = (uint64_t)(((u128)1 << 64) % s.f64);
+    s.upk = ne;
+  } else {
+    return -1;
+  }
+  if (s.upk == 0 || nkeys == 0) return 0;
+  const u128 total = (u128)nkeys * s.upk;
+  int team = 1;
+#ifdef _OPENMP
+  team = omp_get_max_threads();
+#endif
+  uint64_t(*buf)[4] = malloc((size_t)team * (size_t)cap * sizeof *buf);
+  int64_t *cnt = calloc((size_t)team, sizeof *cnt);
+  if (!buf || !cnt) {
+    free(buf);
+    free(cnt);
+    return -1;
+  }
+  int64_t found = 0;
+  u128 done = 0;
+  /* growing slices, each split into one contiguous range per thread: a
+   * thread keeps the first `cap` hits of its range, and the ranges in order
+   * give the first `cap` of the slice */
+  for (uint64_t slice = (uint64_t)1 << 16; done < total && found < cap; slice = slice < ((uint64_t)1 << 28) ? 2 * slice : slice) {
+    const uint64_t c = (total - done < (u128)slice) ? (uint64_t)(total - done) : slice;
+    int ran = 1;
+#pragma omp parallel num_threads(team)
+    {
+      int tid = 0, T = 1;
+#ifdef _OPENMP
+      tid = omp_get_thread_num();
+      T = omp_get_num_threads();
+#endif
+      if (tid == 0) ran = T;
+      const uint64_t lo = c / (uint64_t)T * (uint64_t)tid + (c % (uint64_t)T < (uint64_t)tid ? c % (uint64_t)T : (uint64_t)tid);
+      const uint64_t len = c / (uint64_t)T + ((uint64_t)tid < c % (uint64_t)T);
+      const u128 u0 = done + lo;
+      uint64_t k = (uint64_t)(u0 / s.upk), r = (uint64_t)(u0 % s.upk);
+      int64_t mine = 0;
+      uint64_t hit[2][4];
+      for (uint64_t i = 0; i < len && mine < cap; ++i) {
+        const int got = scan_unit(&s, k, r, hit);
+        for (int j = 0; j < got && mine < cap; ++j) memcpy(buf[(int64_t)tid * cap + mine++], hit[j], sizeof hit[j]);
+        if (++r == s.upk) {
+          r = 0;
+          ++k;
+        }
+      }
+      cnt[tid] = mine;
+    }
+    for (int t = 0; t < ran; ++t)
+      for (int64_t j = 0; j < cnt[t] && found < cap; ++j) memcpy(out + 4 * found++, buf[(int64_t)t * cap + j], sizeof buf[0]);
+    done += c;
+  }
+  free(buf);
+  free(cnt);
+  return found;
+}
+
 int oracle_threads(void) {
 #ifdef _OPENMP
   return omp_get_max_threads();

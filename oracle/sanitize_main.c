@@ -6,7 +6,9 @@
  * Exercises every exported entry point on small inputs: Philox, the
  * closed-form and the program-driven samplers (a hand-built uniform program
  * and a non-uniform one), counts over materialised lists (incl. values >= w),
- * the streaming and the batched counters, and checks they agree.
+ * the streaming and the batched counters, and checks they agree; the
+ * rare-branch scanner with fewer hits than its buffer holds, with more, over
+ * a range that ends inside a slice, and on refused arguments.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -27,6 +29,8 @@ void oracle_batched_counts(int n, uint64_t seed_base, int64_t n_inst, uint64_t c
                            const int32_t *desc0, const uint64_t *pat0, const uint64_t *apat0,
                            const uint64_t *thr0, int nfac1, const int32_t *desc1, const uint64_t *pat1,
                            const uint64_t *apat1, const uint64_t *thr1, int64_t *H, int64_t *Cc, int64_t *P);
+int64_t oracle_scan_rare(int n, int sampler, int kind, int want_h, uint64_t key0, uint64_t nkeys, uint64_t e0,
+                         uint64_t ne, int64_t cap, uint64_t *out);
 
 static int fails = 0;
 #define CHECK(c, msg)                                     \
@@ -97,6 +101,23 @@ int main(void) {
   int64_t tot = 0;
   for (int i = 0; i < 3 * w7; ++i) tot += Pb[i];
   CHECK(tot > 3 * 5003 / 3 && tot < 3 * 5003 * 2 / 3, "batched Q fraction ~ 1/2");
+  /* scanner: n = 11, 3 keys of 2^15 entries; the capped scan is a prefix of the full one */
+  uint64_t(*hits)[4] = calloc(4096, sizeof *hits), few[3][4];
+  const int64_t all = oracle_scan_rare(11, 0, 0, -1, 9, 3, 0, 1 << 15, 4096, &hits[0][0]);
+  CHECK(all > 100 && all < 4096, "w0 fallback entries at n = 11: about 0.28 % of the entries");
+  CHECK(oracle_scan_rare(11, 0, 0, -1, 9, 3, 0, 1 << 15, 3, &few[0][0]) == 3 && !memcmp(few, hits, sizeof few),
+        "capped scan == first hits");
+  for (int64_t i = 1; i < all; ++i)
+    CHECK(hits[i][0] > hits[i - 1][0] || (hits[i][0] == hits[i - 1][0] && hits[i][1] > hits[i - 1][1]), "scan order");
+  const int64_t r1 = oracle_scan_rare(11, 0, 1, 1, 9, 3, 0, 1 << 15, 4096, &hits[0][0]);
+  CHECK(r1 > 0 && r1 < 200, "retry entries on half 1");
+  for (int64_t i = 0; i < r1; ++i) CHECK((hits[i][1] & 1) == 1 && hits[i][3] == 0, "half 1, word 0 of block 1");
+  CHECK(oracle_scan_rare(15, 1, 3, -1, 1, 2, 5, 70001, 4, &hits[0][0]) >= 0, "64-bit scan");
+  CHECK(oracle_scan_rare(12, 0, 0, -1, 0, 1, 0, 64, 1, &hits[0][0]) == -1 &&
+            oracle_scan_rare(11, 0, 0, -1, 0, 1, 1, 64, 1, &hits[0][0]) == -1 &&
+            oracle_scan_rare(15, 1, 0, -1, 0, 1, 0, 64, 1, &hits[0][0]) == -1,
+        "refused arguments");
+  free(hits);
   free(Hb);
   free(Cb);
   free(Pb);

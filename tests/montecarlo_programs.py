@@ -138,10 +138,11 @@ def same_program(a, b):
 
 def twin_lists(info, base, inst, count):
     """[inst, n+1, count] uint8 (read-only): instance i is the C twin's sample of
-    entries [0, count) under key base + i."""
-    n = info["n"]
+    entries [0, count) under key base + i (the closed-form schedule when the
+    program info says so: a shipped program of n <= 11)."""
+    n, closed = info["n"], bool(info.get("closed", False))
     with oracle_lib.single_thread():  # many tiny samples
-        li = np.stack([oracle_lib.sample(n, (base + i) & ((1 << 64) - 1), 0, count, info["notq"], info["q"], False)
+        li = np.stack([oracle_lib.sample(n, (base + i) & ((1 << 64) - 1), 0, count, info["notq"], info["q"], closed)
                        for i in range(inst)]) if inst else np.zeros((0, n + 1, count), np.uint8)
     li = np.ascontiguousarray(li)
     li.setflags(write=False)

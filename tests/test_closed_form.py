@@ -8,24 +8,15 @@ the rest, composed with v_perm_b32).  These tests restate that composition in
 Python and check it against the direct Fisher-Yates decode of every rank
 (n <= 8) or of 20k ranks (n = 9..11).
 """
+import json
 import math
 
 import numpy as np
 import pytest
 
 import oracle_lib
-from conftest import sub
-
-
-def fy_decode(n, R):
-    """Forward Fisher-Yates: digit of position i has radix n-i+1, first most significant."""
-    perm = list(range(16))
-    div = math.factorial(n)
-    for i in range(1, n):
-        div //= n - i + 1
-        d, R = divmod(R, div)
-        perm[i], perm[i + d] = perm[i + d], perm[i]
-    return perm[: n + 1]
+from conftest import GOLDEN, sub
+from sampler_restate import closed_classify, closed_entry_py, fy_decode
 
 
 def tables(n):
@@ -99,42 +90,11 @@ def test_stage_tables_are_permutations(n):
         perm_ok([b(words[offc + i], k) for k in range(4)], 4, 7)
 
 
-def closed_entry_py(n, seed, e):
-    """Python restatement of the closed-form schedule for one entry."""
-    nq = oracle_lib.n_qubits(n)
-    W = 1 << nq
-    p, h = e >> 1, e & 1
-    x = [int(v) for v in oracle_lib.philox(np.array([p & 0xFFFFFFFF, p >> 32, 0, 0], np.uint32), seed)[0]]
-    w0, w1 = x[2 * h], x[2 * h + 1]
-    if not w0 & 1:
-        # group g >= 1: nibble g of the word pair (w1 low nibbles, w1 high
-        # nibbles, w0 high nibbles, byte order); group 0 = group 1
-        vals = [(w1 >> s) & (W - 1) for s in (8, 16, 24, 4, 12, 20, 28)] + \
-               [(w0 >> s) & (W - 1) for s in (4, 12, 20, 28)]
-        return [vals[0]] + vals[: n]
-    nf = math.factorial(n)
-    t32, t27 = (1 << 32) % nf, ((1 << 27) % nf) << 5
-    ok = lambda F, t: (F * nf) & 0xFFFFFFFF >= t  # noqa: E731
-    if ok(w1, t32):
-        F = w1
-    elif ok(w0 & ~31 & 0xFFFFFFFF, t27):
-        F = w0 & ~31 & 0xFFFFFFFF
-    else:
-        a, F = 0, None
-        while F is None:
-            a += 1
-            ys = [int(v) for v in oracle_lib.philox(
-                np.array([p & 0xFFFFFFFF, p >> 32, 0x80000000 + a, h], np.uint32), seed)[0]]
-            F = next((y for y in ys if ok(y, t32)), None)
-    perm = fy_decode(n, (F * nf) >> 32)
-    r = (w0 >> 1) & (W - 1)
-    return [r ^ q for q in perm]
-
-
 def test_closed_rank_fallbacks():
     """The 27-bit second candidate and the retry blocks are reached: find
     entries of each kind at n = 11 and check the oracle against the Python
-    restatement there."""
+    restatement there; at n = 7, 9 and 10 at the positions of the rare-branch
+    fixture."""
     n, seed = 11, 5
     nf = math.factorial(n)
     t32, t27 = (1 << 32) % nf, ((1 << 27) % nf) << 5
@@ -159,6 +119,18 @@ def test_closed_rank_fallbacks():
     for e in kinds.values():
         got = oracle_lib.sample(n, seed, e, 1, info, info, closed=True)
         assert list(got[:, 0]) == closed_entry_py(n, seed, e)
+    # n = 7, 9, 10: no scan of this size meets the branches there (6e-8 per Q entry for the w0 fallback at
+    # n = 7); the positions come from tests/golden/sampler_rare.json, whose records tests/test_sampler_rare.py
+    # holds to the restatement's classification
+    fixture = json.loads((GOLDEN / "sampler_rare.json").read_text())
+    reached = set()
+    for r in fixture["anywhere"] + fixture["small"]:
+        if r["n"] in (7, 9, 10) and r["sampler"] == "closed":
+            kind, _, _, values, _ = closed_classify(r["n"], r["key"], r["entry"])
+            got = oracle_lib.sample(r["n"], r["key"], r["entry"], 1, info, info, closed=True)
+            assert kind == r["kind"] and list(got[:, 0]) == values == r["values"], r
+            reached.add((r["n"], kind))
+    assert {(7, "w0"), (9, "w0"), (10, "w0"), (9, "retry1"), (10, "retry1")} <= reached
 
 
 @pytest.mark.parametrize("n", [1, 3, 7, 8, 11])
