@@ -391,6 +391,48 @@ QBA_API int qba_noise_apply_batched(qba_ctx *ctx, int n_parties, uint64_t seed_b
                                     uint64_t count, uint32_t flip_q16, uint8_t *lists_dev, uint64_t ld,
                                     uint64_t inst_stride, qba_stream stream);
 
+/* Adversary policies: the five deciding calls with the
+ * dishonest parties' behaviour read from a 32-bit policy word `adv`, last in
+ * the argument list.
+ *   bits [0:5)  acts   the actions a dishonest lieutenant draws from, per
+ *                      destination: 0 maybe do not send, 1 replace the order,
+ *                      2 clear P, 3 clear L (tfg.py:266-286), 4 relay unchanged
+ *   bits [8:10) order  what action 1 writes: 0 randint(n + 1) (tfg.py), 1 the
+ *                      smallest order in [0, w) other than the packet's
+ *                      current v (no draw), 2 randint(w)
+ *   bit  12     fresh  0: a mutation stays for the later destinations of the
+ *                      same broadcast (tfg.py); 1: every destination starts
+ *                      from the packet as it was handed to the broadcast
+ *   bit  16     comm   the dishonest commander's split: 0 dest <= (n + 1) / 2
+ *                      gets v1, else v2 (tfg.py:166-185); 1 even dest gets v1
+ * Per destination a dishonest lieutenant draws a = randint(popcount(acts)),
+ * always, and its action is the a-th set bit of acts in ascending order;
+ * action 0 then draws randint(2), action 1 what `order` says, the others
+ * nothing.  QBA_ADV_REFERENCE (0xF) is the rule of the calls without a policy
+ * and gives their rows word for word.  Any other bit set, acts == 0 or order
+ * == 3 is QBA_EINVAL, checked after the count(s) and flip_q16 and before ctx;
+ * every other check, its order, the row layout, asynchrony and capture
+ * legality are those of the call without `_adv`.  The two sampled calls take
+ * flip_q16 as the _noisy calls do (0: no noise) and run one kernel either way.
+ * Specification: montecarlo.AdversaryParty. */
+#define QBA_ADV_REFERENCE 0xFu
+QBA_API int qba_protocol_batched_adv(qba_ctx *ctx, int n_parties, int n_dishonest, uint64_t seed_base,
+                                     int64_t n_instances, const int64_t *H_dev, const int64_t *C_dev,
+                                     const int64_t *P_dev, int32_t *out_dev, qba_stream stream, uint32_t adv);
+QBA_API int qba_montecarlo_lists_adv(qba_ctx *ctx, int n_parties, int n_dishonest, uint64_t seed_base,
+                                     int64_t n_instances, uint64_t count, const uint8_t *lists_dev, uint64_t ld,
+                                     uint64_t inst_stride, int32_t *out_dev, qba_stream stream, uint32_t adv);
+QBA_API int qba_montecarlo_curve_lists_adv(qba_ctx *ctx, int n_parties, int n_dishonest, uint64_t seed_base,
+                                           int64_t n_instances, const uint32_t *counts_host, int n_counts,
+                                           const uint8_t *lists_dev, uint64_t ld, uint64_t inst_stride,
+                                           int32_t *out_dev, qba_stream stream, uint32_t adv);
+QBA_API int qba_montecarlo_sampled_adv(qba_ctx *ctx, int n_parties, int n_dishonest, uint64_t seed_base,
+                                       int64_t n_instances, uint64_t count, uint32_t flip_q16, int32_t *out_dev,
+                                       qba_stream stream, uint32_t adv);
+QBA_API int qba_montecarlo_curve_sampled_adv(qba_ctx *ctx, int n_parties, int n_dishonest, uint64_t seed_base,
+                                             int64_t n_instances, const uint32_t *counts_host, int n_counts,
+                                             uint32_t flip_q16, int32_t *out_dev, qba_stream stream, uint32_t adv);
+
 /* The result rows of the calls above reduced on the device (DESIGN.md section
  * 13.3).  rows_dev is [n_slices][n_instances][4 + 5*(n+1)] int32, contiguous:
  * what a curve call writes, or with n_slices == 1 a single-count call.

@@ -69,6 +69,13 @@ SIGNATURES = {
     "qba_montecarlo_sampled_noisy": [_p, C.c_int, C.c_int, _u64, _i64, _u64, C.c_uint32, _p, _p],
     "qba_montecarlo_curve_sampled_noisy": [_p, C.c_int, C.c_int, _u64, _i64, C.POINTER(C.c_uint32), C.c_int,
                                            C.c_uint32, _p, _p],
+    "qba_protocol_batched_adv": [_p, C.c_int, C.c_int, _u64, _i64, _p, _p, _p, _p, _p, C.c_uint32],
+    "qba_montecarlo_lists_adv": [_p, C.c_int, C.c_int, _u64, _i64, _u64, _p, _u64, _u64, _p, _p, C.c_uint32],
+    "qba_montecarlo_curve_lists_adv": [_p, C.c_int, C.c_int, _u64, _i64, C.POINTER(C.c_uint32), C.c_int, _p, _u64,
+                                       _u64, _p, _p, C.c_uint32],
+    "qba_montecarlo_sampled_adv": [_p, C.c_int, C.c_int, _u64, _i64, _u64, C.c_uint32, _p, _p, C.c_uint32],
+    "qba_montecarlo_curve_sampled_adv": [_p, C.c_int, C.c_int, _u64, _i64, C.POINTER(C.c_uint32), C.c_int,
+                                         C.c_uint32, _p, _p, C.c_uint32],
     "qba_noise_apply_batched": [_p, C.c_int, _u64, _i64, _u64, C.c_uint32, _p, _u64, _u64, _p],
     "qba_montecarlo_curve_shape": [C.c_int, C.POINTER(C.c_int), _pi64, C.POINTER(C.c_int)],
     "qba_montecarlo_program_shape": [_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),

@@ -50,6 +50,9 @@ struct QbaMc {
   QbaMcCounts counts;
   int curve;
   QbaNoise noise;
+  uint32_t adv;  // the policy word, read by the _adv kernels alone (qba_montecarlo_*_adv), which take
+                 // `noise` at run time: steps == 0 is no noise
+  int use_adv;
 };
 
 template <int NP>
@@ -67,6 +70,9 @@ int qba_launch_mc(qba_ctx *ctx, const QbaMc &M);
 // the same through the noisy kernels (qba_mc_noise_inst.hip)
 template <int NP>
 int qba_launch_mc_noisy(qba_ctx *ctx, const QbaMc &M);
+// the same through the adversary-policy kernels (qba_mc_adv_inst.hip)
+template <int NP>
+int qba_launch_mc_adv(qba_ctx *ctx, const QbaMc &M);
 // qba_montecarlo_shape, or (curve) qba_montecarlo_curve_shape
 template <int NP>
 void qba_mc_shape_n(int curve, int *waves, int64_t *lds, int *wgs);

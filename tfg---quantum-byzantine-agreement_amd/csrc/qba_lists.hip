@@ -3,6 +3,7 @@
 #include <type_traits>
 
 #include "qba_lists.h"
+#include "qba_proto_adv.h"
 
 // Experiment builds only (tools/exp): restrict instantiation to one n.
 #ifndef QBA_ONLY_N
@@ -122,6 +123,7 @@ static int mc_sampled(qba_ctx *ctx, int n, QbaMc &M) {
   if (M.n_inst == 0) return QBA_OK;
   if (int rc = qba_set_device(ctx)) return rc;
   M.ps = (const QbaProgramSet *)ctx->prog_dev[n];
+  if (M.use_adv) return with_n(n, [&](auto k) { return qba_launch_mc_adv<decltype(k)::value>(ctx, M); });
   if (M.noise.steps)
     return with_n(n, [&](auto k) { return qba_launch_mc_noisy<decltype(k)::value>(ctx, M); });
   return with_n(n, [&](auto k) { return qba_launch_mc<decltype(k)::value>(ctx, M); });
@@ -129,20 +131,25 @@ static int mc_sampled(qba_ctx *ctx, int n, QbaMc &M) {
 
 // The single-count and the curve call, noiseless (flip_q16 0: the noiseless
 // kernel) or noisy, behind the names they are exported under.
+// `adv` (NULL: no policy) picks the _adv kernels, under the policy word it points to.
 static int mc_one(const char *who, qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst, uint64_t count,
-                  uint32_t flip_q16, int32_t *out, qba_stream stream) {
-  QbaMc M{who, nullptr, seed_base, n_inst, n_dis, out, (hipStream_t)stream, {{(uint32_t)count}, 1}, 0, {}};
+                  uint32_t flip_q16, int32_t *out, qba_stream stream, const uint32_t *adv = nullptr) {
+  QbaMc M{who, nullptr, seed_base, n_inst, n_dis, out, (hipStream_t)stream, {{(uint32_t)count}, 1}, 0, {},
+          adv ? *adv : 0u, adv != nullptr};
   const char *bad = count >> 31 ? "count must be < 2^31" : bad_flip(flip_q16);
+  if (!bad && adv) bad = qba_adv_bad(*adv);
   if (int rc = qba_mc_check(who, ctx, n, n_dis, bad, n_inst, out)) return rc;
   if (flip_q16) M.noise = qba_noise_of(flip_q16);
   return mc_sampled(ctx, n, M);
 }
 
 static int mc_curve(const char *who, qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
-                    const uint32_t *counts, int n_counts, uint32_t flip_q16, int32_t *out, qba_stream stream) {
-  QbaMc M{who, nullptr, seed_base, n_inst, n_dis, out, (hipStream_t)stream, {}, 1, {}};
-  if (int rc = qba_mc_curve_check(who, ctx, n, n_dis, n_inst, counts, n_counts, out, &M.counts, bad_flip(flip_q16)))
-    return rc;
+                    const uint32_t *counts, int n_counts, uint32_t flip_q16, int32_t *out, qba_stream stream,
+                    const uint32_t *adv = nullptr) {
+  QbaMc M{who, nullptr, seed_base, n_inst, n_dis, out, (hipStream_t)stream, {}, 1, {}, adv ? *adv : 0u, adv != nullptr};
+  const char *bad = bad_flip(flip_q16);
+  if (!bad && adv) bad = qba_adv_bad(*adv);
+  if (int rc = qba_mc_curve_check(who, ctx, n, n_dis, n_inst, counts, n_counts, out, &M.counts, bad)) return rc;
   if (flip_q16) M.noise = qba_noise_of(flip_q16);
   return mc_sampled(ctx, n, M);
 }
@@ -169,6 +176,21 @@ extern "C" int qba_montecarlo_curve_sampled_noisy(qba_ctx *ctx, int n, int n_dis
                                                   int32_t *out, qba_stream stream) {
   return mc_curve("qba_montecarlo_curve_sampled_noisy", ctx, n, n_dis, seed_base, n_inst, counts, n_counts, flip_q16,
                   out, stream);
+}
+
+// The two under an adversary policy word: the noisy
+// calls' arguments, then the word, checked after flip_q16 and before ctx.
+extern "C" int qba_montecarlo_sampled_adv(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
+                                          uint64_t count, uint32_t flip_q16, int32_t *out, qba_stream stream,
+                                          uint32_t adv) {
+  return mc_one("qba_montecarlo_sampled_adv", ctx, n, n_dis, seed_base, n_inst, count, flip_q16, out, stream, &adv);
+}
+
+extern "C" int qba_montecarlo_curve_sampled_adv(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
+                                                const uint32_t *counts, int n_counts, uint32_t flip_q16,
+                                                int32_t *out, qba_stream stream, uint32_t adv) {
+  return mc_curve("qba_montecarlo_curve_sampled_adv", ctx, n, n_dis, seed_base, n_inst, counts, n_counts, flip_q16,
+                  out, stream, &adv);
 }
 
 // The flips of the noisy Monte-Carlo calls into lists in the layout of

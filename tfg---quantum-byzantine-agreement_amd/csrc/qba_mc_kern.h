@@ -17,6 +17,7 @@
 #pragma once
 #include "qba_lists_launch.h"
 #include "qba_noise.h"
+#include "qba_proto_adv.h"
 #include "qba_proto_rounds.h"
 
 constexpr size_t QBA_MC_CU_LDS = 160 * 1024;  // LDS of a CU, and the most one workgroup may take
@@ -352,23 +353,173 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64, NW * 64)))
 }
 
 
+// ---------------------------------------------------------------------------
+// qba_k_mc_sampled_adv / qba_k_mc_curve_sampled_adv: the two sampled kernels
+// with the rounds under an adversary policy word (proto_rounds_adv,
+// qba_proto_adv.h).  They take the noise of 13.5 at run
+// time: nz.steps == 0 (flip_q16 == 0) skips the draw under a wave-uniform
+// branch, so one instantiation per (n, sampler, form) serves both.  The policy
+// is a scalar and takes no LDS: the launch shape is the noiseless kernel's.
+// Texts of their own, instantiated by qba_mc_adv_inst.hip alone.
+// ---------------------------------------------------------------------------
+template <int NP, int SAMP, int NW>
+__global__ void __attribute__((amdgpu_flat_work_group_size(64, NW * 64)))
+    qba_k_mc_sampled_adv(const QbaProgramSet *__restrict__ ps, uint64_t seed_base, int64_t n_inst, uint32_t count,
+                           int n_dis, int nw_run, int32_t *__restrict__ out, const QbaNoise nz, uint32_t adv) {
+  using C = QCfg<NP>;
+  constexpr int ND = CF<NP>::ND;
+  extern __shared__ __align__(16) uint64_t lds[];
+  const uint64_t *pat, *apat, *thr;
+  const uint32_t *pl;
+  uint32_t *waves = qba_stage<NP, 1, SAMP, NW * 64>(ps, lds, pat, apat, thr, pl);
+  __syncthreads();
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = (int)__lane_id();
+  if (wv >= nw_run) return;  // tables larger than the shape was compiled for: fewer waves have room
+  uint32_t *mine = waves + (size_t)wv * (qba_mc_wave_lds(C::G, C::W) / sizeof(uint32_t));
+  ProtoShared &S = *reinterpret_cast<ProtoShared *>(mine);
+  uint32_t *box = mine + PROTO_S_WORDS;
+  const int64_t stride = (int64_t)gridDim.x * nw_run;
+  for (int64_t inst = (int64_t)blockIdx.x * nw_run + wv; inst < n_inst; inst += stride) {
+    const uint64_t key = seed_base + (uint64_t)inst;
+    const uint32_t k0 = __builtin_amdgcn_readfirstlane((uint32_t)key);
+    const uint32_t k1 = __builtin_amdgcn_readfirstlane((uint32_t)(key >> 32));
+    proto_sync<false>();  // the previous instance's row stores have read S
+    mc_begin(S, box, C::G, C::W, lane);
+    proto_sync<false>();
+    uint32_t seen = 0, bad = 0;
+    if constexpr (SAMP == QBA_S_CLOSED) {
+      // lane l takes pairs l, l + 64, ...: one Philox block, two entries (the
+      // second half of the last block of an odd count stays unused)
+      const uint32_t npair = (count + 1u) >> 1;
+      for (uint32_t p = (uint32_t)lane; p < npair; p += 64u) {
+        const QbaU4 x = qba_philox(p, 0u, 0u, 0u, k0, k1);
+#pragma unroll
+        for (uint32_t h = 0; h < 2; ++h) {
+          if (2u * p + h >= count) break;
+          uint32_t d[ND], D[4] = {0u, 0u, 0u, 0u};
+          qba_closed_half<NP>(h ? x.z : x.x, h ? x.w : x.y, (uint64_t)p, h, k0, k1, pl, d);
+#pragma unroll
+          for (int i = 0; i < ND; ++i) D[i] = d[i];
+          if (nz.steps) qba_noise_d<C::G, C::W>(qba_noise_r(2u * p + h, 0u, k0, k1, nz), D);
+          mc_entry<false>(S, box, D, C::G, C::W, seen, bad);
+        }
+      }
+    } else {
+      for (uint32_t e = (uint32_t)lane; e < count; e += 64u) {
+        uint32_t d[ND], D[4] = {0u, 0u, 0u, 0u};
+        qba_entry_d<NP, SAMP>((uint64_t)e, k0, k1, ps, pat, apat, thr, pl, d);
+#pragma unroll
+        for (int i = 0; i < ND; ++i) D[i] = d[i];
+        if (nz.steps) qba_noise_d<C::G, C::W>(qba_noise_r(e, 0u, k0, k1, nz), D);
+        mc_entry<false>(S, box, D, C::G, C::W, seen, bad);
+      }
+    }
+    mc_flags(box, C::G, C::W, seen, bad);
+    proto_sync<false>();
+    uint32_t st;
+    const uint32_t pnz = mc_finish<false>(S, box, C::G, C::W, lane, st);
+    proto_sync<false>();
+    proto_rounds_adv<false>(S, box, NP, n_dis, key, pnz, st, lane, out + inst * (int64_t)(4 + 5 * C::G), adv);
+  }
+}
+
+template <int NP, int SAMP, int NW>
+__global__ void __attribute__((amdgpu_flat_work_group_size(64, NW * 64)))
+    qba_k_mc_curve_sampled_adv(const QbaProgramSet *__restrict__ ps, uint64_t seed_base, int64_t n_inst, int n_dis,
+                                 int nw_run, int32_t *__restrict__ out, const QbaMcCounts cv, const QbaNoise nz,
+                               uint32_t adv) {
+  using C = QCfg<NP>;
+  constexpr int ND = CF<NP>::ND;
+  constexpr size_t WAVE_WORDS = (qba_mc_wave_lds(C::G, C::W) + qba_mc_acc_lds(C::G, C::W)) / sizeof(uint32_t);
+  extern __shared__ __align__(16) uint64_t lds[];
+  const uint64_t *pat, *apat, *thr;
+  const uint32_t *pl;
+  uint32_t *waves = qba_stage<NP, 1, SAMP, NW * 64>(ps, lds, pat, apat, thr, pl);
+  __syncthreads();
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = (int)__lane_id();
+  if (wv >= nw_run) return;
+  uint32_t *mine = waves + (size_t)wv * WAVE_WORDS;
+  ProtoShared &S = *reinterpret_cast<ProtoShared *>(mine);
+  uint32_t *box = mine + PROTO_S_WORDS;
+  uint32_t *acc = mine + qba_mc_wave_lds(C::G, C::W) / sizeof(uint32_t);
+  uint32_t *mcw = acc + C::W * C::G;  // the AND words and the flags, as mc_entry addresses them
+  const int64_t stride = (int64_t)gridDim.x * nw_run;
+  for (int64_t inst = (int64_t)blockIdx.x * nw_run + wv; inst < n_inst; inst += stride) {
+    const uint64_t key = seed_base + (uint64_t)inst;
+    const uint32_t k0 = __builtin_amdgcn_readfirstlane((uint32_t)key);
+    const uint32_t k1 = __builtin_amdgcn_readfirstlane((uint32_t)(key >> 32));
+    mc_acc_begin(acc, C::G, C::W, lane);  // nothing but the segments touches the area
+    uint32_t seen = 0, bad = 0, lo = 0;
+    for (int j = 0; j < cv.n; ++j) {
+      const uint32_t hi = cv.c[j];
+      proto_sync<false>();  // the area is set up; the previous row's stores have read S
+      if constexpr (SAMP == QBA_S_CLOSED) {
+        // pairs [lo / 2, ceil(hi / 2)), lane l the l-th, l + 64-th, ... of them;
+        // a checkpoint at an odd count splits a pair, whose block is then drawn
+        // in both segments and gives each its half
+        const uint32_t pend = (hi + 1u) >> 1;
+        for (uint32_t p = (lo >> 1) + (uint32_t)lane; p < pend; p += 64u) {
+          const QbaU4 x = qba_philox(p, 0u, 0u, 0u, k0, k1);
+#pragma unroll
+          for (uint32_t h = 0; h < 2; ++h) {
+            const uint32_t e = 2u * p + h;
+            if (e < lo || e >= hi) continue;
+            uint32_t d[ND], D[4] = {0u, 0u, 0u, 0u};
+            qba_closed_half<NP>(h ? x.z : x.x, h ? x.w : x.y, (uint64_t)p, h, k0, k1, pl, d);
+#pragma unroll
+            for (int i = 0; i < ND; ++i) D[i] = d[i];
+            if (nz.steps) qba_noise_d<C::G, C::W>(qba_noise_r(e, 0u, k0, k1, nz), D);
+            mc_entry_at<false>(acc, C::G, mcw, D, C::G, C::W, seen, bad);
+          }
+        }
+      } else {
+        for (uint32_t e = lo + (uint32_t)lane; e < hi; e += 64u) {
+          uint32_t d[ND], D[4] = {0u, 0u, 0u, 0u};
+          qba_entry_d<NP, SAMP>((uint64_t)e, k0, k1, ps, pat, apat, thr, pl, d);
+#pragma unroll
+          for (int i = 0; i < ND; ++i) D[i] = d[i];
+          if (nz.steps) qba_noise_d<C::G, C::W>(qba_noise_r(e, 0u, k0, k1, nz), D);
+          mc_entry_at<false>(acc, C::G, mcw, D, C::G, C::W, seen, bad);
+        }
+      }
+      mc_flags(mcw, C::G, C::W, seen, bad);
+      proto_sync<false>();
+      uint32_t st;
+      const uint32_t pnz = mc_acc_finish<false>(S, acc, C::G, C::W, lane, st);
+      proto_sync<false>();
+      proto_rounds_adv<false>(S, box, NP, n_dis, key, pnz, st, lane,
+                              out + ((int64_t)j * n_inst + inst) * (int64_t)(4 + 5 * C::G), adv);
+      lo = hi;
+    }
+    proto_sync<false>();  // the last finish has read the area
+  }
+}
+
+
 // The sampled kernel of (NP, SAMP) for one count (qba_k_mc_sampled) or for a
 // curve (qba_k_mc_curve_sampled), or (NOISE) the noisy form of either, as the
 // host sees it; everything below is written once over this.  The noisy kernels
 // keep the launch shape of the noiseless ones: noise takes no LDS.
-template <int NP, int SAMP_, bool CURVE_, bool NOISE_ = false>
+template <int NP, int SAMP_, bool CURVE_, bool NOISE_ = false, bool ADV_ = false>
 struct QbaMcKern {
   using C = QCfg<NP>;
   static constexpr int SAMP = SAMP_;
   static constexpr bool CURVE = CURVE_;
   static constexpr bool NOISE = NOISE_;
+  static constexpr bool ADV = ADV_;  // the _adv kernels: noise at run time, then the policy word
   // LDS of a wave beside its ProtoShared and mailbox
   static constexpr size_t EXTRA = CURVE ? qba_mc_acc_lds(C::G, C::W) : 0;
   // waves per workgroup the kernel is compiled for
   static constexpr int NW = qba_mc_shape(qba_mc_tables<NP, SAMP>(), C::G, C::W, 16, EXTRA).waves;
   static_assert(NW >= 1, "no room for a wave beside the tables");
   static const void *kernel() {
-    if constexpr (CURVE && NOISE)
+    if constexpr (CURVE && ADV)
+      return (const void *)qba_k_mc_curve_sampled_adv<NP, SAMP, NW>;
+    else if constexpr (ADV)
+      return (const void *)qba_k_mc_sampled_adv<NP, SAMP, NW>;
+    else if constexpr (CURVE && NOISE)
       return (const void *)qba_k_mc_curve_sampled_noisy<NP, SAMP, NW>;
     else if constexpr (NOISE)
       return (const void *)qba_k_mc_sampled_noisy<NP, SAMP, NW>;
@@ -395,9 +546,9 @@ static int qba_launch_mc_s(qba_ctx *ctx, const QbaMc &M, size_t tables) {
   const int grid = (int)(need < cap ? need : cap);
   const int nw_run = sh.waves;
   // qba_k_mc_sampled takes the one count where qba_k_mc_curve_sampled takes them all, last;
-  // the noisy forms take the noise after that
-  const void *one[] = {&M.ps, &M.seed_base, &M.n_inst, &M.counts.c[0], &M.n_dis, &nw_run, &M.out, &M.noise};
-  const void *all[] = {&M.ps, &M.seed_base, &M.n_inst, &M.n_dis, &nw_run, &M.out, &M.counts, &M.noise};
+  // the noisy forms take the noise after that, the _adv forms the noise and then the policy word
+  const void *one[] = {&M.ps, &M.seed_base, &M.n_inst, &M.counts.c[0], &M.n_dis, &nw_run, &M.out, &M.noise, &M.adv};
+  const void *all[] = {&M.ps, &M.seed_base, &M.n_inst, &M.n_dis, &nw_run, &M.out, &M.counts, &M.noise, &M.adv};
   QBA_HIP(hipLaunchKernel(K::kernel(), dim3(grid), dim3(K::NW * 64), const_cast<void **>(K::CURVE ? all : one), sh.lds,
                           M.stream));
   QBA_HIP(hipGetLastError());
@@ -432,19 +583,26 @@ static int qba_mc_with_curve(bool curve, const F &f) {
 }
 
 // f(QbaMcKern of the program compiled for NP, tables)
-template <int NP, bool NOISE = false, class F>
+template <int NP, bool NOISE = false, bool ADV = false, class F>
 static int qba_mc_with_kern(qba_ctx *ctx, bool curve, const F &f) {
   return qba_mc_with_curve(curve, [&](auto c) {
     return qba_mc_with_program<NP>(ctx, [&](auto s, size_t tables) {
-      return f(QbaMcKern<NP, decltype(s)::value, decltype(c)::value, NOISE>(), tables);
+      return f(QbaMcKern<NP, decltype(s)::value, decltype(c)::value, NOISE, ADV>(), tables);
     });
   });
 }
 
 // The noiseless kernels are instantiated by qba_lists_inst.hip, the noisy ones
 // by qba_mc_noise_inst.hip: code objects of their own, so that those of the
-// list kernels stay what they were.
-#ifndef QBA_MC_NOISY_INST
+// list kernels stay what they were; the _adv ones by qba_mc_adv_inst.hip.
+#if defined(QBA_MC_ADV_INST)
+template <int NP>
+int qba_launch_mc_adv(qba_ctx *ctx, const QbaMc &M) {
+  return qba_mc_with_kern<NP, false, true>(ctx, M.curve, [&](auto k, size_t tables) {
+    return qba_launch_mc_s<decltype(k)>(ctx, M, tables);
+  });
+}
+#elif !defined(QBA_MC_NOISY_INST)
 template <int NP>
 int qba_launch_mc(qba_ctx *ctx, const QbaMc &M) {
   return qba_mc_with_kern<NP>(ctx, M.curve, [&](auto k, size_t tables) {

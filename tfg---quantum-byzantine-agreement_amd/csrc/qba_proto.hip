@@ -16,7 +16,7 @@
 //             CountTables.desc / consistent consult)
 //   qba_k_mc_lists: lane l distils entries l, l + 64, ... of the instance's
 //             rows into the same masks (mc_entry, qba_proto_rounds.h)
-#include "qba_proto_rounds.h"
+#include "qba_proto_adv.h"  // the entry points' policy check and launches; the kernels here keep qba_proto_rounds.h
 
 namespace {
 
@@ -256,5 +256,55 @@ extern "C" int qba_montecarlo_curve_lists(qba_ctx *ctx, int n, int n_dis, uint64
   return launch_chunks(ctx, n_inst, [&](int64_t first, dim3 grid) {
     hipLaunchKernelGGL(qba_k_mc_curve_lists, grid, dim3(QBA_PROTO_BLOCK), lds, (hipStream_t)stream, n, n_dis,
                        seed_base, first, n_inst, lists, ld, inst_stride, out, cv);
+  });
+}
+
+// ---------------------------------------------------------------------------
+// The same three calls under an adversary policy word (qba_proto_adv.h,
+// DESIGN.md section 13.7): the kernels of qba_proto_adv.hip.  The word is
+// checked where the count is, before ctx is looked at.
+// ---------------------------------------------------------------------------
+extern "C" int qba_protocol_batched_adv(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
+                                        const int64_t *H, const int64_t *C, const int64_t *P, int32_t *out,
+                                        qba_stream stream, uint32_t adv) {
+  const char *who = "qba_protocol_batched_adv";
+  if (int rc = qba_mc_check(who, ctx, n, n_dis, qba_adv_bad(adv), n_inst, out)) return rc;
+  if (n_inst == 0) return QBA_OK;
+  if (!H || !C || !P) return qba_fail(QBA_EINVAL, std::string(who) + ": a table pointer is NULL");
+  const int G = n + 1, w = 1 << qba_nq(n);
+  const size_t lds = (size_t)(PROTO_S_WORDS + proto_box_words(G, w)) * sizeof(uint32_t);  // <= 34960 B
+  return launch_chunks(ctx, n_inst, [&](int64_t first, dim3 grid) {
+    qba_launch_protocol_adv(grid, lds, (hipStream_t)stream, n, n_dis, seed_base, first, H, C, P, out, adv);
+  });
+}
+
+extern "C" int qba_montecarlo_lists_adv(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
+                                        uint64_t count, const uint8_t *lists, uint64_t ld, uint64_t inst_stride,
+                                        int32_t *out, qba_stream stream, uint32_t adv) {
+  const char *who = "qba_montecarlo_lists_adv";
+  int rc = qba_mc_check(who, ctx, n, n_dis, count >> 31 ? "count must be < 2^31" : qba_adv_bad(adv), n_inst, out);
+  if (rc || (rc = lists_check(who, n, n_inst, count, lists, ld, inst_stride)) || n_inst == 0) return rc;
+  const int G = n + 1, w = 1 << qba_nq(n);
+  const size_t lds = (size_t)(PROTO_S_WORDS + proto_box_words(G, w)) * sizeof(uint32_t);  // <= 34960 B
+  return launch_chunks(ctx, n_inst, [&](int64_t first, dim3 grid) {
+    qba_launch_mc_lists_adv(grid, lds, (hipStream_t)stream, n, n_dis, seed_base, first, (uint32_t)count, lists, ld,
+                            inst_stride, out, adv);
+  });
+}
+
+extern "C" int qba_montecarlo_curve_lists_adv(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
+                                              const uint32_t *counts, int n_counts, const uint8_t *lists,
+                                              uint64_t ld, uint64_t inst_stride, int32_t *out, qba_stream stream,
+                                              uint32_t adv) {
+  const char *who = "qba_montecarlo_curve_lists_adv";
+  QbaMcCounts cv;
+  int rc = qba_mc_curve_check(who, ctx, n, n_dis, n_inst, counts, n_counts, out, &cv, qba_adv_bad(adv));
+  if (rc || (rc = lists_check(who, n, n_inst, cv.c[cv.n - 1], lists, ld, inst_stride)) || n_inst == 0) return rc;
+  const int G = n + 1, w = 1 << qba_nq(n);
+  const size_t lds = (size_t)(PROTO_S_WORDS + ((proto_box_words(G, w) + 3) & ~3) + mc_acc_words(G, w)) *
+                     sizeof(uint32_t);  // <= 37024 B
+  return launch_chunks(ctx, n_inst, [&](int64_t first, dim3 grid) {
+    qba_launch_mc_curve_lists_adv(grid, lds, (hipStream_t)stream, n, n_dis, seed_base, first, n_inst, lists, ld,
+                                  inst_stride, out, cv, adv);
   });
 }

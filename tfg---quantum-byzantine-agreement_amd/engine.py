@@ -291,12 +291,25 @@ class Engine:
             call(name, self.ctx, n, _u64(seed_base), n_inst, count, *rest)
         return lists, counts
 
+    @staticmethod
+    def _check_adversary(adversary) -> Optional[int]:
+        """None, or the checked policy word (montecarlo.adversary; DESIGN.md
+        section 13.7) that sends a call to its ``_adv`` entry point."""
+        if adversary is None:
+            return None
+        from .montecarlo import check_adversary
+        return check_adversary(adversary)
+
     def protocol_batched(self, n: int, n_dishonest: int, seed_base: int, counts: Counts,
-                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                         out: Optional[torch.Tensor] = None, adversary: Optional[int] = None) -> torch.Tensor:
         """The protocol rounds of every instance of ``counts`` (the per-instance
         tables of sample_check_batched) in one launch (tfg.py:101-125, 166-196,
-        266-306, 337-363): int32 [n_inst, 4 + 5*(n+1)], layout in qba.h."""
+        266-306, 337-363): int32 [n_inst, 4 + 5*(n+1)], layout in qba.h.
+        ``adversary=word`` (qba_protocol_batched_adv): the dishonest parties
+        follow that policy (montecarlo.adversary); None is the reference's rule
+        through the call that existed before, 0xF the same rows."""
         self._check_n(n)
+        adv = self._check_adversary(adversary)
         _, w = self.sizes(n)
         g = n + 1
         n_inst = counts.P.shape[0] if counts.P.dim() == 2 else -1
@@ -305,6 +318,10 @@ class Engine:
                     t.device != self.device:
                 raise QbaError("counts must be contiguous int64 [n_inst, ...] tensors of sample_check_batched")
         out = self._rows_out(n, n_inst, out)
+        if adv is not None:
+            call("qba_protocol_batched_adv", self.ctx, n, n_dishonest, seed_base, n_inst, _ptr(counts.H),
+                 _ptr(counts.C), _ptr(counts.P), _ptr(out), self.stream(), adv)
+            return out
         call("qba_protocol_batched", self.ctx, n, n_dishonest, seed_base, n_inst, _ptr(counts.H), _ptr(counts.C),
              _ptr(counts.P), _ptr(out), self.stream())
         return out
@@ -363,19 +380,26 @@ class Engine:
         return int(flip_q16)
 
     def montecarlo_sampled(self, n: int, n_dishonest: int, seed_base: int, n_inst: int, count: int,
-                           out: Optional[torch.Tensor] = None, flip_q16: int = 0) -> torch.Tensor:
+                           out: Optional[torch.Tensor] = None, flip_q16: int = 0,
+                           adversary: Optional[int] = None) -> torch.Tensor:
         """n_inst instances (key seed_base + i) of `count` entries sampled,
         distilled and decided in one kernel (qba_montecarlo_sampled): the rows
         of protocol_batched(sample_check_batched(...)), int32
         [n_inst, 4 + 5*(n+1)], with no list buffer and no count tables.
         ``flip_q16=k > 0`` (qba_montecarlo_sampled_noisy): every measured bit of
-        an entry flips with probability k / 65536 first (montecarlo.noise_masks)."""
+        an entry flips with probability k / 65536 first (montecarlo.noise_masks).
+        ``adversary=word`` (qba_montecarlo_sampled_adv, with or without noise):
+        as in protocol_batched."""
         self._check_n(n)
         self._check_curve(n, n_dishonest, n_inst, [count])
         flip = self._check_flip(flip_q16)
+        adv = self._check_adversary(adversary)
         self.prepare(n)
         out = self._rows_out(n, n_inst, out)
-        if flip:
+        if adv is not None:
+            call("qba_montecarlo_sampled_adv", self.ctx, n, n_dishonest, _u64(seed_base), n_inst, count, flip,
+                 _ptr(out), self.stream(), adv)
+        elif flip:
             call("qba_montecarlo_sampled_noisy", self.ctx, n, n_dishonest, _u64(seed_base), n_inst, count, flip,
                  _ptr(out), self.stream())
         else:
@@ -399,34 +423,46 @@ class Engine:
         return lists
 
     def montecarlo_lists(self, n: int, n_dishonest: int, seed_base: int, lists, count: int,
-                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                         out: Optional[torch.Tensor] = None, adversary: Optional[int] = None) -> torch.Tensor:
         """The same rows from injected lists (qba_montecarlo_lists): a uint8
         [n_inst, n+1, >= count] device tensor in the layout of
         sample_check_batched, or a host array of that shape (copied to the
         device).  A row's status 4 marks a value >= w at a Q-correlated
-        position (montecarlo.ST_RANGE)."""
+        position (montecarlo.ST_RANGE).  ``adversary=word``
+        (qba_montecarlo_lists_adv): as in protocol_batched."""
         self._check_n(n)
         self._check_curve(n, n_dishonest, 0, [count])
+        adv = self._check_adversary(adversary)
         lists, n_inst, ld, stride = self._mc_lists(n, lists, count)
         out = self._rows_out(n, n_inst, out)
+        if adv is not None:
+            call("qba_montecarlo_lists_adv", self.ctx, n, n_dishonest, _u64(seed_base), n_inst, count, _ptr(lists), ld,
+                 stride, _ptr(out), self.stream(), adv)
+            return out
         call("qba_montecarlo_lists", self.ctx, n, n_dishonest, _u64(seed_base), n_inst, count, _ptr(lists), ld, stride,
              _ptr(out), self.stream())
         return out
 
     # -- a whole sizeL curve in one pass (qba_montecarlo_curve_*) ------------------
     def montecarlo_curve_sampled(self, n: int, n_dishonest: int, seed_base: int, n_inst: int, counts,
-                                 out: Optional[torch.Tensor] = None, flip_q16: int = 0) -> torch.Tensor:
+                                 out: Optional[torch.Tensor] = None, flip_q16: int = 0,
+                                 adversary: Optional[int] = None) -> torch.Tensor:
         """The n_inst instances of montecarlo_sampled decided at every count of
         the strictly increasing ``counts`` (at most 32) in one pass over their
         entries (qba_montecarlo_curve_sampled): int32 [len(counts), n_inst,
         4 + 5*(n+1)], slice j word for word montecarlo_sampled(count=counts[j]),
-        with ``flip_q16`` as there (qba_montecarlo_curve_sampled_noisy)."""
+        with ``flip_q16`` as there (qba_montecarlo_curve_sampled_noisy) and
+        ``adversary`` as there (qba_montecarlo_curve_sampled_adv)."""
         self._check_n(n)
         cs = self._check_curve(n, n_dishonest, n_inst, counts)
         flip = self._check_flip(flip_q16)
+        adv = self._check_adversary(adversary)
         self.prepare(n)
         out = self._rows_out(n, n_inst, out, len(cs))
-        if flip:
+        if adv is not None:
+            call("qba_montecarlo_curve_sampled_adv", self.ctx, n, n_dishonest, _u64(seed_base), n_inst,
+                 (C.c_uint32 * len(cs))(*cs), len(cs), flip, _ptr(out), self.stream(), adv)
+        elif flip:
             call("qba_montecarlo_curve_sampled_noisy", self.ctx, n, n_dishonest, _u64(seed_base), n_inst,
                  (C.c_uint32 * len(cs))(*cs), len(cs), flip, _ptr(out), self.stream())
         else:
@@ -435,15 +471,21 @@ class Engine:
         return out
 
     def montecarlo_curve_lists(self, n: int, n_dishonest: int, seed_base: int, lists, counts,
-                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                               out: Optional[torch.Tensor] = None, adversary: Optional[int] = None) -> torch.Tensor:
         """The same from injected lists (qba_montecarlo_curve_lists), uint8
         [n_inst, n+1, >= counts[-1]] as montecarlo_lists takes them: slice j is
         montecarlo_lists(count=counts[j]).  A value >= w at Q-correlated
-        position k gives status 4 in exactly the slices with counts[j] > k."""
+        position k gives status 4 in exactly the slices with counts[j] > k.
+        ``adversary=word`` (qba_montecarlo_curve_lists_adv): as in protocol_batched."""
         self._check_n(n)
         cs = self._check_curve(n, n_dishonest, 0, counts)
+        adv = self._check_adversary(adversary)
         lists, n_inst, ld, stride = self._mc_lists(n, lists, cs[-1])
         out = self._rows_out(n, n_inst, out, len(cs))
+        if adv is not None:
+            call("qba_montecarlo_curve_lists_adv", self.ctx, n, n_dishonest, _u64(seed_base), n_inst,
+                 (C.c_uint32 * len(cs))(*cs), len(cs), _ptr(lists), ld, stride, _ptr(out), self.stream(), adv)
+            return out
         call("qba_montecarlo_curve_lists", self.ctx, n, n_dishonest, _u64(seed_base), n_inst,
              (C.c_uint32 * len(cs))(*cs), len(cs), _ptr(lists), ld, stride, _ptr(out), self.stream())
         return out

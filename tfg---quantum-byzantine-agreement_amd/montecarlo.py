@@ -41,9 +41,17 @@ definition; the fused kernels draw the same flips inside
 (``Engine.sample_check_batched(..., flip_q16=k)``, ``run(path="tables_noisy")``:
 the noisy lists and their count tables stay on the device for the caller), and
 ``Engine.noise_apply`` XORs them into device lists.
+
+Adversary policies (``adversary=word`` on the calls below; DESIGN.md section
+13.7): what a dishonest lieutenant does to a packet per destination and how a
+dishonest commander splits the lieutenants, as a 32-bit word built by
+:func:`adversary` (presets in :data:`ADVERSARIES`).  :class:`AdversaryParty`
+is the definition; ``0xF`` is the reference's rule, and ``None`` (the default
+everywhere) calls exactly what was called before policies existed.
 """
 from __future__ import annotations
 
+import copy
 from typing import Callable, Dict, Optional
 
 import numpy as np
@@ -202,8 +210,149 @@ def noisy_lists(n: int, key: int, lists, flip_q16: int) -> np.ndarray:
     return L ^ noise_masks(n, key, L.shape[1], flip_q16)
 
 
+# ---------------------------------------------------------------------------
+# Adversary policies
+# ---------------------------------------------------------------------------
+ACT_MUTE, ACT_REORDER, ACT_CLEAR_P, ACT_CLEAR_L, ACT_RELAY = range(5)
+ORDER_REFERENCE, ORDER_LOW, ORDER_W = range(3)
+ADV_REFERENCE = 0xF
+_ADV_VALID = 0x0001131F
+
+
+def check_adversary(word) -> int:
+    """``word`` as an int when it is a valid policy word; QbaError otherwise
+    (a reserved bit, no allowed action, or order 3)."""
+    try:
+        a = int(word)
+    except (TypeError, ValueError):
+        raise QbaError(f"adversary must be an integer policy word, not {word!r}") from None
+    if a < 0 or a & ~_ADV_VALID:
+        raise QbaError(f"adversary word {a:#x} sets a reserved bit")
+    if not a & 0x1F:
+        raise QbaError(f"adversary word {a:#x} allows no action (acts == 0)")
+    if (a >> 8) & 3 > 2:
+        raise QbaError(f"adversary word {a:#x}: the order field must be <= 2")
+    return a
+
+
+def adversary(acts=(ACT_MUTE, ACT_REORDER, ACT_CLEAR_P, ACT_CLEAR_L), order: int = ORDER_REFERENCE,
+              fresh: bool = False, comm: bool = False) -> int:
+    """The policy word of a dishonest party.
+
+    ``acts``   the actions a dishonest lieutenant draws from, uniformly, per
+               destination (a set of 0..4, or their bit mask): 0 maybe do not
+               send, 1 replace the order, 2 clear P, 3 clear L (the reference's
+               four), 4 relay unchanged.
+    ``order``  what action 1 writes: 0 ``randint(n + 1)`` (the reference), 1 the
+               smallest order in [0, w) other than the packet's current v
+               (0, or 1 when v is 0; no draw), 2 ``randint(w)``.
+    ``fresh``  False: a mutation stays for the later destinations of the same
+               broadcast (the reference).  True: every destination starts from
+               the packet as it was handed to the broadcast.
+    ``comm``   the dishonest commander's split: False ``dest <= (n + 1) / 2``
+               gets v1 (the reference), True even ``dest`` gets v1.
+
+    The defaults give ``0xF``, the reference's traitor."""
+    if isinstance(acts, int):
+        mask = acts
+    else:
+        mask = 0
+        for a in acts:
+            if not 0 <= int(a) <= 4:
+                raise QbaError(f"action {a!r} outside 0..4")
+            mask |= 1 << int(a)
+    if not 0 <= mask < 32:
+        raise QbaError(f"acts {mask:#x} outside the five action bits")
+    if order not in (0, 1, 2):
+        raise QbaError("order is 0 (randint(n + 1)), 1 (low) or 2 (randint(w))")
+    return check_adversary(mask | int(order) << 8 | (1 << 12 if fresh else 0) | (1 << 16 if comm else 0))
+
+
+ADVERSARIES = {
+    "reference": ADV_REFERENCE,
+    "relay": adversary([ACT_RELAY]),
+    "reorder_low": adversary([ACT_REORDER], order=ORDER_LOW, fresh=True, comm=True),
+    "mute": adversary([ACT_MUTE]),
+    "strip": adversary([ACT_CLEAR_P, ACT_CLEAR_L], fresh=True),
+}
+
+
+def parse_adversary(text) -> int:
+    """A preset name of :data:`ADVERSARIES` or a number (``0x...`` or decimal)
+    as a checked policy word."""
+    if isinstance(text, str):
+        if text in ADVERSARIES:
+            return ADVERSARIES[text]
+        try:
+            text = int(text, 0)
+        except ValueError:
+            raise QbaError(f"adversary {text!r} is neither a number nor one of {sorted(ADVERSARIES)}") from None
+    return check_adversary(text)
+
+
+class AdversaryParty(CountParty):
+    """CountParty whose dishonest behaviour is read from the policy word
+    ``adv`` (a class attribute: :func:`adversary_party` makes the subclass of a
+    word).  The specification of the ``_adv`` kernels.
+
+    Per destination a dishonest lieutenant draws ``a = randint(popcount(acts))``
+    -- always, also when one action is allowed -- and takes the a-th set bit of
+    ``acts`` in ascending order as its action; action 0 then draws
+    ``randint(2)``, action 1 what ``order`` says, the others nothing.  With
+    ``0xF`` this is Party.lieu_broadcast / comm_broadcast draw for draw."""
+
+    adv = ADV_REFERENCE
+
+    def comm_broadcast(self):
+        if self.rank != 1 or not self.dishonest or not (self.adv >> 16) & 1:
+            return super().comm_broadcast()
+        v1 = self.rng.randint(self.w)
+        v2 = self.rng.randint(self.w)
+        while v2 == v1:
+            v2 = self.rng.randint(self.w)
+        for dest in range(2, self.n + 1):
+            v = v1 if dest % 2 == 0 else v2
+            self.send(dest, self.p_for(v), v, set())
+
+    def lieu_broadcast(self, P, v, L):
+        acts = [a for a in range(5) if (self.adv >> a) & 1]
+        order, fresh = (self.adv >> 8) & 3, (self.adv >> 12) & 1
+        P0, v0, L0 = P, v, L
+        for dest in range(2, self.n + 1):
+            if dest == self.rank:
+                continue
+            go = 1
+            if self.dishonest:
+                if fresh:  # P.clear() and L.clear() mutate in place: a copy per destination
+                    P, v, L = copy.copy(P0), v0, set(L0)
+                action = acts[self.rng.randint(len(acts))]
+                if action == ACT_MUTE:
+                    go = self.rng.randint(2)
+                elif action == ACT_REORDER:
+                    if order == ORDER_LOW:
+                        v = 1 if int(v) == 0 else 0
+                    else:
+                        v = self.rng.randint(self.n + 1 if order == ORDER_REFERENCE else self.w)
+                elif action == ACT_CLEAR_P:
+                    P.clear()
+                elif action == ACT_CLEAR_L:
+                    L.clear()
+            if go:
+                self.send(dest, P, v, L)
+
+
+def adversary_party(word: int, base=None):
+    """The :class:`AdversaryParty` subclass of the policy ``word``, for the
+    ``party_cls`` seam of :func:`run_host`; ``base`` (a CountParty subclass, for
+    instance an observing one) is mixed in behind it."""
+    word = check_adversary(word)
+    bases = (AdversaryParty,) if base in (None, CountParty, AdversaryParty) else (AdversaryParty, base)
+    return type(f"AdversaryParty_{word:x}", bases, {"adv": word})
+
+
 def run_host(n: int, sizeL: int, n_dishonest: int, n_inst: int, seed_base: int, engine, lists=None,
-             party_cls=None, rng_factory: Optional[Callable] = None, flip_q16: int = 0) -> np.ndarray:
+             party_cls=None, rng_factory: Optional[Callable] = None, flip_q16: int = 0,
+             adversary: Optional[int] = None) -> np.ndarray:
     """The specification of qba_protocol_batched: CountParty under
     ``protocol.run_local`` (LocalWorld's barrier-epoch delivery: a round's inbox
     is everything sent in the previous epoch, in (source, sequence) order,
@@ -218,8 +367,14 @@ def run_host(n: int, sizeL: int, n_dishonest: int, n_inst: int, seed_base: int, 
     ``flip_q16 > 0``: :func:`noisy_lists` of the lists the instance would have
     used (injected, or else sampled by ``engine.sample(n, key, 0, sizeL)``,
     which the engine must then offer), then the same.
+
+    ``adversary=word``: the dishonest parties follow that policy
+    (:func:`adversary_party` of ``party_cls``); ``None`` is the reference's
+    rule, and ``0xF`` gives the same rows.
     """
     flip = _check_flip(flip_q16)
+    if adversary is not None:
+        party_cls = adversary_party(adversary, party_cls)
     out = np.zeros((n_inst, out_words(n)), np.int32)
     make = rng_factory or ProtocolRng
     for i in range(n_inst):
@@ -455,7 +610,8 @@ def masks_from_lists(n: int, lists) -> dict:
 
 
 def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, packed: bool = True,
-        batch: int = 4096, path: str = "tables", tally: bool = False, failures: int = 0, flip_q16: int = 0) -> dict:
+        batch: int = 4096, path: str = "tables", tally: bool = False, failures: int = 0, flip_q16: int = 0,
+        adversary: Optional[int] = None) -> dict:
     """``runs`` independent instances on the device, ``batch`` at a time, batch
     at offset ``off`` under key ``seed + off``; only the result rows are copied
     to the host.  Returns :func:`summarize` of all rows.
@@ -477,37 +633,43 @@ def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, pack
     measured bit flips with probability k / 65536.  ``"tables_noisy"`` is the
     tables path through the noisy batched sampler
     (``sample_check_batched(..., flip_q16=k)``): the same rows as ``"fused"``;
-    with ``flip_q16=0`` it is ``"tables"``."""
+    with ``flip_q16=0`` it is ``"tables"``.
+
+    ``adversary=word`` (any path): the dishonest parties follow that policy
+    (:func:`adversary`); the decisions go through the ``_adv`` kernels."""
     if path not in ("tables", "fused", "tables_noisy"):
         raise ValueError("path is 'tables', 'fused' or 'tables_noisy'")
     noise = {"flip_q16": _check_flip(flip_q16)} if flip_q16 else {}
     if noise and path == "tables":
         raise ValueError("flip_q16 > 0 needs path='fused' or path='tables_noisy'")
+    adv = {} if adversary is None else {"adversary": check_adversary(adversary)}
     lists = None
 
     def decide(key, b, out=None):
         nonlocal lists
         into = {} if out is None else {"out": out[0]}
         if path == "fused":
-            return engine.montecarlo_sampled(n, n_dishonest, key, b, sizeL, **into, **noise)
+            return engine.montecarlo_sampled(n, n_dishonest, key, b, sizeL, **into, **noise, **adv)
         buf, counts = engine.sample_check_batched(n, key, b, sizeL, None if lists is None else lists[:b],
                                                   packed=packed, **noise)
         if lists is None:
             lists = buf
-        return engine.protocol_batched(n, n_dishonest, key, counts, **into)
+        return engine.protocol_batched(n, n_dishonest, key, counts, **into, **adv)
     return _batches(n, 1, runs, batch, seed, engine, decide, tally, failures)[0]
 
 
 def curve_host(n: int, counts, n_dishonest: int, n_inst: int, seed_base: int, engine, lists=None,
-               flip_q16: int = 0) -> np.ndarray:
+               flip_q16: int = 0, adversary: Optional[int] = None) -> np.ndarray:
     """The specification of the curve calls: the stack of :func:`run_host` at
     each count of ``counts``, int32 [len(counts), n_inst, out_words(n)].
     Injected ``lists`` [n_inst, n+1, >= max(counts)] are truncated to
     ``[:, :, :c]`` for the count c.  ``flip_q16`` as in :func:`run_host` (the
-    flips of entry e are the same at every count)."""
+    flips of entry e are the same at every count), and ``adversary``."""
     counts = [int(c) for c in counts]
     li = None if lists is None else np.asarray(lists)
     noise = {"flip_q16": flip_q16} if flip_q16 else {}
+    if adversary is not None:
+        noise["adversary"] = adversary
     rows = [run_host(n, c, n_dishonest, n_inst, seed_base, engine, lists=None if li is None else li[:, :, :c],
                      **noise)
             for c in counts]
@@ -515,15 +677,18 @@ def curve_host(n: int, counts, n_dishonest: int, n_inst: int, seed_base: int, en
 
 
 def curve(n: int, counts, n_dishonest: int, runs: int, seed: int, engine, batch: int = 4096, tally: bool = False,
-          failures: int = 0, flip_q16: int = 0) -> dict:
+          failures: int = 0, flip_q16: int = 0, adversary: Optional[int] = None) -> dict:
     """The failure curve over sizeL: ``runs`` instances, ``batch`` at a time as
     :func:`run` keys them, each decided at every sizeL of the strictly
     increasing ``counts`` by one montecarlo_curve_sampled call per batch.
     Returns ``{sizeL: summarize(...)}`` in checkpoint order; the summary at
     sizeL = c is that of ``run(n, c, ..., path="fused")``.  ``tally`` and
-    ``failures`` as in :func:`run`, per checkpoint; ``flip_q16`` as there."""
+    ``failures`` as in :func:`run`, per checkpoint; ``flip_q16`` and
+    ``adversary`` as there."""
     counts = [int(c) for c in counts]
     noise = {"flip_q16": _check_flip(flip_q16)} if flip_q16 else {}
+    if adversary is not None:
+        noise["adversary"] = check_adversary(adversary)
     if tally or failures:
         engine._check_curve(n, n_dishonest, 0, counts)  # before any device buffer: an empty list has no slice
 

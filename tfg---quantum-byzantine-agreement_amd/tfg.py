@@ -83,6 +83,10 @@ def _args(argv):
                     help="with --runs: sample and count each batch's lists in the batched sampler, then decide them "
                          "(montecarlo.run path='tables_noisy'): with --flip K the noisy lists and tables, the same "
                          "instances and summary as the fused kernels'; not with --curve or --fused")
+    ap.add_argument("--adversary", default=None, metavar="NAME|0xHEX",
+                    help="with --runs: the dishonest parties follow this policy, a preset (reference, relay, "
+                         "reorder_low, mute, strip) or a policy word (montecarlo.adversary); the summary lines "
+                         "end in adversary=0xWORD")
     ap.add_argument("--quiet", action="store_true", help="print only the outcome")
     ap.add_argument("--timing", action="store_true", help="print the wall time of the run")
     ap.add_argument("--wire", action="store_true",
@@ -112,6 +116,14 @@ def _args(argv):
         if not 0 <= a.flip <= 65535:
             ap.error("--flip: K must be in [0, 65535] (out of 65536)")
         a.fused = not a.tables
+    if a.adversary is not None:
+        if a.runs is None:
+            ap.error("--adversary needs --runs")
+        from . import montecarlo
+        try:
+            a.adversary = montecarlo.parse_adversary(a.adversary)
+        except montecarlo.QbaError as e:
+            ap.error(f"--adversary: {e}")
     return a
 
 
@@ -235,6 +247,9 @@ def _montecarlo(a, eng, size_l) -> int:
     if a.flip:
         how["flip_q16"] = a.flip
     noise = f" flip={a.flip}/65536" if a.flip else ""
+    if a.adversary is not None:
+        how["adversary"] = a.adversary
+        noise += f" adversary={a.adversary:#x}"
     if a.curve is not None:
         points = montecarlo.curve(a.parties, a.curve, a.nDishonest, a.runs, seed, eng, batch=a.batch, **how)
     else:

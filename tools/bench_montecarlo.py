@@ -38,6 +38,14 @@ instances x n = 7 x sizeL = 1e5, 2 dishonest, on one GPU.
       The rows of the two routes are compared; a route is called faster only
       where the min-max ranges are apart.
 
+  --adversary NAME|0xHEX  (repeatable) another mode, per --sizeL: the fused call
+      through the policy entry point (qba_montecarlo_sampled_adv) at the
+      reference word 0xF -- the rows of the call without a policy, which is
+      checked, so that column is the cost of the policy kernels' text -- and at
+      each policy given, beside the call without a policy, which is timed first
+      and again last in the same session.  Other policies run another protocol:
+      their times are reported without a verdict.
+
 (a), (b), (d), the --tally calls, the --flip calls and the --curve pair are device-event times of single calls on warm code: median, min
 and max over --repeats launches after --warmup launches.  (c) is host wall
 time around runs that end in device synchronisation (each reads its tables
@@ -94,12 +102,19 @@ def main(argv=None) -> int:
     ap.add_argument("--tables", action="store_true",
                     help="with --flip: time the noisy batched call, the same followed by protocol_batched, and the "
                          "noisy fused call at each --sizeL and K, and compare their rows")
+    ap.add_argument("--adversary", action="append", default=None, metavar="NAME|0xHEX",
+                    help="time montecarlo_sampled through the policy entry point at 0xF and at each policy given, "
+                         "beside the call without a policy, at each --sizeL; repeatable; nothing else is measured")
     a = ap.parse_args(argv)
+    if a.adversary and (a.flip or a.curve or a.tally or a.tables):
+        ap.error("--adversary goes with --sizeL alone")
     if a.tables and (not a.flip or a.curve or a.tally):
         ap.error("--tables needs --flip and goes with neither --curve nor --tally")
 
     eng = importlib.import_module(f"{PKG}.engine").Engine(0)
-    if a.tables:
+    if a.adversary:
+        lines = [json.dumps(_measure_adversary(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
+    elif a.tables:
         lines = [json.dumps(_measure_flip_tables(a, eng, size_l, k)) for size_l in (a.sizeL or [100_000])
                  for k in a.flip]
     elif a.flip:
@@ -191,6 +206,40 @@ def _measure_flip(a, eng, counts, curve: bool) -> dict:
     res["noiseless_spread_at_median"] = abs(res["noiseless"]["median_ms"] - res["noiseless_again"]["median_ms"]) / base
     for t in res["flips"].values():
         t["over_noiseless_at_median"] = t["median_ms"] / base
+    return res
+
+
+def _measure_adversary(a, eng, size_l) -> dict:
+    """--adversary: the policy call at 0xF and at each policy beside the call without one."""
+    import torch
+    mc = importlib.import_module(f"{PKG}.montecarlo")
+    n, nd, inst = a.parties, a.dishonest, a.instances
+    rows = eng.montecarlo_sampled(n, nd, a.seed, inst, size_l)
+    ref = rows.clone()
+    res = {"config": {"n": n, "sizeL": size_l, "dishonest": nd, "instances": inst, "seed": a.seed,
+                      "device": torch.cuda.get_device_name(0)}}
+    res["no_policy"] = _events(lambda: eng.montecarlo_sampled(n, nd, a.seed, inst, size_l, rows), a.warmup, a.repeats)
+    res["policies"] = {}
+    for name in ["reference"] + [p for p in a.adversary if p != "reference"]:
+        word = mc.parse_adversary(name)
+        t = _events(lambda: eng.montecarlo_sampled(n, nd, a.seed, inst, size_l, rows, adversary=word), a.warmup,
+                    a.repeats)
+        t["word"] = f"{word:#x}"
+        t["rows_equal_no_policy"] = bool(torch.equal(rows, ref))
+        t["successes"] = int(rows[:, 0].sum())
+        res["policies"][name] = t
+    res["no_policy_again"] = _events(lambda: eng.montecarlo_sampled(n, nd, a.seed, inst, size_l, rows), a.warmup,
+                                     a.repeats)
+    first, last = res["no_policy"], res["no_policy_again"]
+    base = min(first["median_ms"], last["median_ms"])
+    res["no_policy_spread_at_median"] = abs(first["median_ms"] - last["median_ms"]) / base
+    for t in res["policies"].values():
+        t["over_no_policy_at_median"] = t["median_ms"] / base
+    r = res["policies"]["reference"]
+    lo, hi = min(first["min_ms"], last["min_ms"]), max(first["max_ms"], last["max_ms"])
+    # a verdict only for 0xF (equal rows), and only where the min-max ranges do not overlap
+    res["reference_word_slower"] = r["min_ms"] > hi
+    res["reference_word_faster"] = r["max_ms"] < lo
     return res
 
 
