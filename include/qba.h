@@ -433,6 +433,45 @@ QBA_API int qba_montecarlo_curve_sampled_adv(qba_ctx *ctx, int n_parties, int n_
                                              int64_t n_instances, const uint32_t *counts_host, int n_counts,
                                              uint32_t flip_q16, int32_t *out_dev, qba_stream stream, uint32_t adv);
 
+/* A grid of scenarios per checkpoint in one pass.  A
+ * scenario is a pair (n_dishonest, adv).  The two calls are
+ * qba_montecarlo_curve_sampled_adv / qba_montecarlo_curve_lists_adv deciding
+ * every instance at every checkpoint under every scenario scen_host[0 ..
+ * n_scen): the entries are sampled (or read) and distilled once, and at each
+ * checkpoint the rounds run once per scenario on the same masks.  Instance i at
+ * checkpoint j under scenario s writes 4 + 5*(n+1) int32 at
+ *   out_dev + (((int64_t)j * n_scen + s) * n_instances + i) * (4 + 5*(n+1)),
+ * word for word (status included) the row the _adv curve call writes at
+ * counts_host[j] with n_dishonest = scen_host[s].n_dishonest and adv =
+ * scen_host[s].adv: out_dev is [n_counts][n_scen][n_instances][4 + 5*(n+1)],
+ * contiguous, and qba_montecarlo_tally takes it as n_counts * n_scen slices.
+ * Under one key the traitors at n_dishonest = k are the first k of those at
+ * k + 1 (a partial Fisher-Yates), so scenarios that differ in n_dishonest run
+ * on nested traitor sets, the same lists and the same commander's order.
+ * Checked in this order, each QBA_EINVAL: n_parties; the checkpoint list as
+ * the curve calls check it; flip_q16 (sampled form); scen_host not NULL and
+ * 1 <= n_scen <= QBA_MC_SWEEP_MAX; n_counts * n_scen <= QBA_MC_CURVE_MAX;
+ * then scenario 0, 1, ...: n_dishonest in [0, n_parties], then adv as the _adv
+ * calls check it; then ctx, n_instances and out_dev as those calls.  Equal
+ * scenarios are legal and give equal slices.  Both host arrays travel by
+ * value in the kernel arguments and may be reused when the call returns.
+ * Asynchronous on `stream`, allocate and copy nothing, legal in a stream
+ * capture.  The launch shape of the sampled form is
+ * qba_montecarlo_curve_shape's.  Specification: montecarlo.sweep_host. */
+#define QBA_MC_SWEEP_MAX 16
+typedef struct {
+  int32_t n_dishonest;
+  uint32_t adv;
+} qba_mc_scenario;
+QBA_API int qba_montecarlo_sweep_sampled(qba_ctx *ctx, int n_parties, uint64_t seed_base, int64_t n_instances,
+                                         const uint32_t *counts_host, int n_counts,
+                                         const qba_mc_scenario *scen_host, int n_scen, uint32_t flip_q16,
+                                         int32_t *out_dev, qba_stream stream);
+QBA_API int qba_montecarlo_sweep_lists(qba_ctx *ctx, int n_parties, uint64_t seed_base, int64_t n_instances,
+                                       const uint32_t *counts_host, int n_counts, const qba_mc_scenario *scen_host,
+                                       int n_scen, const uint8_t *lists_dev, uint64_t ld, uint64_t inst_stride,
+                                       int32_t *out_dev, qba_stream stream);
+
 /* The result rows of the calls above reduced on the device (DESIGN.md section
  * 13.3).  rows_dev is [n_slices][n_instances][4 + 5*(n+1)] int32, contiguous:
  * what a curve call writes, or with n_slices == 1 a single-count call.

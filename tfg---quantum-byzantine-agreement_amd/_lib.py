@@ -26,6 +26,12 @@ _i32, _i64, _u64, _f64 = C.c_int32, C.c_int64, C.c_uint64, C.c_double
 _p = C.c_void_p
 _pi32, _pi64, _pu64, _pf64 = C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_u64), C.POINTER(_f64)
 
+
+class Scenario(C.Structure):
+    """qba_mc_scenario: one (n_dishonest, policy word) of a sweep call."""
+    _fields_ = [("n_dishonest", C.c_int32), ("adv", C.c_uint32)]
+
+
 # name -> argtypes (restype is int unless listed in _RESTYPE)
 SIGNATURES = {
     "qba_last_error": [],
@@ -76,6 +82,10 @@ SIGNATURES = {
     "qba_montecarlo_sampled_adv": [_p, C.c_int, C.c_int, _u64, _i64, _u64, C.c_uint32, _p, _p, C.c_uint32],
     "qba_montecarlo_curve_sampled_adv": [_p, C.c_int, C.c_int, _u64, _i64, C.POINTER(C.c_uint32), C.c_int,
                                          C.c_uint32, _p, _p, C.c_uint32],
+    "qba_montecarlo_sweep_sampled": [_p, C.c_int, _u64, _i64, C.POINTER(C.c_uint32), C.c_int, C.POINTER(Scenario),
+                                     C.c_int, C.c_uint32, _p, _p],
+    "qba_montecarlo_sweep_lists": [_p, C.c_int, _u64, _i64, C.POINTER(C.c_uint32), C.c_int, C.POINTER(Scenario),
+                                   C.c_int, _p, _u64, _u64, _p, _p],
     "qba_noise_apply_batched": [_p, C.c_int, _u64, _i64, _u64, C.c_uint32, _p, _u64, _u64, _p],
     "qba_montecarlo_curve_shape": [C.c_int, C.POINTER(C.c_int), _pi64, C.POINTER(C.c_int)],
     "qba_montecarlo_program_shape": [_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),

@@ -267,6 +267,19 @@ struct QbaMcCounts {
 // before ctx is looked at; NULL: nothing); fills `cv`
 int qba_mc_curve_check(const char *who, qba_ctx *ctx, int n, int n_dis, int64_t n_inst, const uint32_t *counts,
                        int n_counts, const void *out, QbaMcCounts *cv, const char *bad_other = nullptr);
+// The scenarios of a sweep call, by value in the
+// kernel arguments as the checkpoints are
+struct QbaMcScen {
+  qba_mc_scenario s[QBA_MC_SWEEP_MAX];
+  int n;
+};
+// That envelope for qba_montecarlo_sweep_sampled / _lists: n_parties, the
+// checkpoint list, `bad_flip`, the scenario list (pointer, n_scen, n_counts *
+// n_scen, then scenario 0, 1, ...: n_dishonest, adv), then ctx, n_instances
+// and out; fills `cv` and `sv`
+int qba_mc_sweep_check(const char *who, qba_ctx *ctx, int n, int64_t n_inst, const uint32_t *counts, int n_counts,
+                       const qba_mc_scenario *scen, int n_scen, const char *bad_flip, const void *out,
+                       QbaMcCounts *cv, QbaMcScen *sv);
 
 static inline int qba_nq(int n) {  // ceil(log2(n+1)), tfg.py:317
   int q = 0;

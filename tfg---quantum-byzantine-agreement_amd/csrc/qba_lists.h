@@ -53,6 +53,7 @@ struct QbaMc {
   uint32_t adv;  // the policy word, read by the _adv kernels alone (qba_montecarlo_*_adv), which take
                  // `noise` at run time: steps == 0 is no noise
   int use_adv;
+  QbaMcScen scen;  // read by the sweep kernel alone (qba_montecarlo_sweep_sampled), which takes no n_dis / adv
 };
 
 template <int NP>
@@ -73,6 +74,9 @@ int qba_launch_mc_noisy(qba_ctx *ctx, const QbaMc &M);
 // the same through the adversary-policy kernels (qba_mc_adv_inst.hip)
 template <int NP>
 int qba_launch_mc_adv(qba_ctx *ctx, const QbaMc &M);
+// the curve under every scenario of M.scen, through the sweep kernel (qba_mc_sweep_inst.hip)
+template <int NP>
+int qba_launch_mc_sweep(qba_ctx *ctx, const QbaMc &M);
 // qba_montecarlo_shape, or (curve) qba_montecarlo_curve_shape
 template <int NP>
 void qba_mc_shape_n(int curve, int *waves, int64_t *lds, int *wgs);

@@ -193,6 +193,25 @@ extern "C" int qba_montecarlo_curve_sampled_adv(qba_ctx *ctx, int n, int n_dis, 
                   out, stream, &adv);
 }
 
+// The curve call under every scenario of a list: one
+// pass over the entries, the rounds once per checkpoint and scenario.  Checked
+// in the order counts, flip_q16, scenarios, ctx (qba_mc_sweep_check).
+extern "C" int qba_montecarlo_sweep_sampled(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst,
+                                            const uint32_t *counts, int n_counts, const qba_mc_scenario *scen,
+                                            int n_scen, uint32_t flip_q16, int32_t *out, qba_stream stream) {
+  const char *who = "qba_montecarlo_sweep_sampled";
+  QbaMc M{who, nullptr, seed_base, n_inst, 0, out, (hipStream_t)stream, {}, 1, {}, 0u, 0, {}};
+  if (int rc = qba_mc_sweep_check(who, ctx, n, n_inst, counts, n_counts, scen, n_scen, bad_flip(flip_q16), out,
+                                  &M.counts, &M.scen))
+    return rc;
+  if (flip_q16) M.noise = qba_noise_of(flip_q16);
+  if (int rc = need_program(ctx, n, who)) return rc;
+  if (n_inst == 0) return QBA_OK;
+  if (int rc = qba_set_device(ctx)) return rc;
+  M.ps = (const QbaProgramSet *)ctx->prog_dev[n];
+  return with_n(n, [&](auto k) { return qba_launch_mc_sweep<decltype(k)::value>(ctx, M); });
+}
+
 // The flips of the noisy Monte-Carlo calls into lists in the layout of
 // qba_sample_check_batched, in place (qba_noise.hip); its argument checks,
 // after flip_q16.  Needs no program: it samples nothing.

@@ -219,6 +219,34 @@ int qba_mc_curve_check(const char *who, qba_ctx *ctx, int n, int n_dis, int64_t 
   return QBA_OK;
 }
 
+int qba_mc_sweep_check(const char *who, qba_ctx *ctx, int n, int64_t n_inst, const uint32_t *counts, int n_counts,
+                       const qba_mc_scenario *scen, int n_scen, const char *bad_flip, const void *out,
+                       QbaMcCounts *cv, QbaMcScen *sv) {
+  std::string at;  // "scenario i: what": the envelope reports the first bad scenario by its index
+  const char *bad = bad_counts(counts, n_counts);
+  if (!bad) bad = bad_flip;
+  if (!bad) {
+    if (!scen) bad = "scen is NULL";
+    else if (n_scen < 1 || n_scen > QBA_MC_SWEEP_MAX) bad = "n_scen must be in [1, 16]";
+    else if (n_counts * n_scen > QBA_MC_CURVE_MAX) bad = "n_counts * n_scen must be <= 32";
+  }
+  for (int s = 0; !bad && s < n_scen; ++s) {
+    const char *b = scen[s].n_dishonest < 0 || scen[s].n_dishonest > n ? "n_dishonest must be in [0, n_parties]"
+                                                                       : qba_adv_bad(scen[s].adv);
+    if (!b) continue;
+    at = "scenario " + std::to_string(s) + ": " + b;
+    bad = at.c_str();
+  }
+  if (int rc = qba_mc_check(who, ctx, n, 0, bad, n_inst, out)) return rc;
+  *cv = QbaMcCounts{};
+  for (int j = 0; j < n_counts; ++j) cv->c[j] = counts[j];
+  cv->n = n_counts;
+  *sv = QbaMcScen{};
+  for (int s = 0; s < n_scen; ++s) sv->s[s] = scen[s];
+  sv->n = n_scen;
+  return QBA_OK;
+}
+
 // The injected rows of the two list calls hold `need` entries (the count, or
 // the last checkpoint) per row without overlapping.
 static int lists_check(const char *who, int n, int64_t n_inst, uint64_t need, const uint8_t *lists, uint64_t ld,
@@ -306,5 +334,25 @@ extern "C" int qba_montecarlo_curve_lists_adv(qba_ctx *ctx, int n, int n_dis, ui
   return launch_chunks(ctx, n_inst, [&](int64_t first, dim3 grid) {
     qba_launch_mc_curve_lists_adv(grid, lds, (hipStream_t)stream, n, n_dis, seed_base, first, n_inst, lists, ld,
                                   inst_stride, out, cv, adv);
+  });
+}
+
+// qba_montecarlo_curve_lists_adv under every scenario of a list at every
+// checkpoint: the kernel of qba_proto_sweep.hip.
+extern "C" int qba_montecarlo_sweep_lists(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst,
+                                          const uint32_t *counts, int n_counts, const qba_mc_scenario *scen,
+                                          int n_scen, const uint8_t *lists, uint64_t ld, uint64_t inst_stride,
+                                          int32_t *out, qba_stream stream) {
+  const char *who = "qba_montecarlo_sweep_lists";
+  QbaMcCounts cv;
+  QbaMcScen sv;
+  int rc = qba_mc_sweep_check(who, ctx, n, n_inst, counts, n_counts, scen, n_scen, nullptr, out, &cv, &sv);
+  if (rc || (rc = lists_check(who, n, n_inst, cv.c[cv.n - 1], lists, ld, inst_stride)) || n_inst == 0) return rc;
+  const int G = n + 1, w = 1 << qba_nq(n);
+  const size_t lds = (size_t)(PROTO_S_WORDS + ((proto_box_words(G, w) + 3) & ~3) + mc_acc_words(G, w)) *
+                     sizeof(uint32_t);  // <= 37024 B
+  return launch_chunks(ctx, n_inst, [&](int64_t first, dim3 grid) {
+    qba_launch_mc_sweep_lists(grid, lds, (hipStream_t)stream, n, seed_base, first, n_inst, lists, ld, inst_stride,
+                              out, cv, sv);
   });
 }

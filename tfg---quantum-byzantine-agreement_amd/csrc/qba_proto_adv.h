@@ -52,6 +52,10 @@ void qba_launch_mc_lists_adv(dim3 grid, size_t lds, hipStream_t stream, int n, i
 void qba_launch_mc_curve_lists_adv(dim3 grid, size_t lds, hipStream_t stream, int n, int n_dis, uint64_t seed_base,
                                    int64_t first, int64_t n_inst, const uint8_t *lists, uint64_t ld,
                                    uint64_t inst_stride, int32_t *out, const QbaMcCounts &cv, uint32_t adv);
+// ... and of qba_proto_sweep.hip's (the curve under every scenario of `sv`)
+void qba_launch_mc_sweep_lists(dim3 grid, size_t lds, hipStream_t stream, int n, uint64_t seed_base, int64_t first,
+                               int64_t n_inst, const uint8_t *lists, uint64_t ld, uint64_t inst_stride, int32_t *out,
+                               const QbaMcCounts &cv, const QbaMcScen &sv);
 
 namespace {
 

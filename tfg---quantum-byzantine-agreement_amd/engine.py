@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import resource
-from ._lib import KIND_NOTQ, KIND_Q, MAX_PARTIES, QbaError, call, lib
+from ._lib import KIND_NOTQ, KIND_Q, MAX_PARTIES, QbaError, Scenario, call, lib
 
 
 def _ptr(t: torch.Tensor) -> C.c_void_p:
@@ -489,6 +489,75 @@ class Engine:
         call("qba_montecarlo_curve_lists", self.ctx, n, n_dishonest, _u64(seed_base), n_inst,
              (C.c_uint32 * len(cs))(*cs), len(cs), _ptr(lists), ld, stride, _ptr(out), self.stream())
         return out
+
+    # -- a grid of scenarios per checkpoint in one pass (qba_montecarlo_sweep_*) ----
+    SWEEP_MAX = 16  # QBA_MC_SWEEP_MAX
+
+    @classmethod
+    def _check_sweep(cls, n: int, n_inst: int, counts, scenarios):
+        """The argument check of the two montecarlo_sweep_* methods: the
+        checkpoints as a list of ints and the scenarios as a list of
+        ``(n_dishonest, word)``."""
+        cs = cls._check_curve(n, 0, n_inst, counts)
+        try:
+            sc = [(int(k), word) for k, word in scenarios]
+        except (TypeError, ValueError):
+            raise QbaError("scenarios must be a sequence of (n_dishonest, policy word) pairs") from None
+        if not 1 <= len(sc) <= cls.SWEEP_MAX:
+            raise QbaError(f"between 1 and {cls.SWEEP_MAX} scenarios, not {len(sc)}")
+        if len(cs) * len(sc) > cls.CURVE_MAX:
+            raise QbaError(f"len(counts) * len(scenarios) must be <= {cls.CURVE_MAX}, not {len(cs) * len(sc)}")
+        for i, (k, word) in enumerate(sc):
+            if not 0 <= k <= n:
+                raise QbaError(f"scenario {i}: n_dishonest={k} outside [0, {n}]")
+            sc[i] = (k, cls._check_adversary(word))
+            if sc[i][1] is None:
+                raise QbaError(f"scenario {i}: the policy word is None (0xF is the reference's traitor)")
+        return cs, sc
+
+    @staticmethod
+    def _scen_array(sc):
+        return (Scenario * len(sc))(*(Scenario(k, word) for k, word in sc))
+
+    def montecarlo_sweep_sampled(self, n: int, seed_base: int, n_inst: int, counts, scenarios,
+                                 out: Optional[torch.Tensor] = None, flip_q16: int = 0) -> torch.Tensor:
+        """The n_inst instances of montecarlo_curve_sampled decided at every
+        count of ``counts`` under every scenario ``(n_dishonest, word)`` of
+        ``scenarios`` (at most 16, and at most 32 slices in all) in one pass
+        over their entries (qba_montecarlo_sweep_sampled): int32 [len(counts),
+        len(scenarios), n_inst, 4 + 5*(n+1)], slice (j, s) word for word
+        montecarlo_curve_sampled(..., adversary=word)[j] with that n_dishonest.
+        ``flip_q16`` as there."""
+        self._check_n(n)
+        cs, sc = self._check_sweep(n, n_inst, counts, scenarios)
+        flip = self._check_flip(flip_q16)
+        self.prepare(n)
+        out = self._sweep_out(n, n_inst, out, len(cs), len(sc))
+        call("qba_montecarlo_sweep_sampled", self.ctx, n, _u64(seed_base), n_inst, (C.c_uint32 * len(cs))(*cs),
+             len(cs), self._scen_array(sc), len(sc), flip, _ptr(out), self.stream())
+        return out
+
+    def montecarlo_sweep_lists(self, n: int, seed_base: int, lists, counts, scenarios,
+                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The same from injected lists (qba_montecarlo_sweep_lists), as
+        montecarlo_curve_lists takes them: slice (j, s) is
+        montecarlo_curve_lists(..., adversary=word)[j] with that n_dishonest."""
+        self._check_n(n)
+        cs, sc = self._check_sweep(n, 0, counts, scenarios)
+        lists, n_inst, ld, stride = self._mc_lists(n, lists, cs[-1])
+        out = self._sweep_out(n, n_inst, out, len(cs), len(sc))
+        call("qba_montecarlo_sweep_lists", self.ctx, n, _u64(seed_base), n_inst, (C.c_uint32 * len(cs))(*cs),
+             len(cs), self._scen_array(sc), len(sc), _ptr(lists), ld, stride, _ptr(out), self.stream())
+        return out
+
+    def _sweep_out(self, n: int, n_inst: int, out: Optional[torch.Tensor], k: int, s: int) -> torch.Tensor:
+        """``out`` as [k, s, n_inst, words], or a new buffer when it is None; a
+        contiguous [k * s, n_inst, words] buffer (the slices as
+        montecarlo_tally takes them) is taken as well."""
+        words = 4 + 5 * (n + 1)
+        if isinstance(out, torch.Tensor) and out.is_contiguous() and tuple(out.shape) == (k, s, n_inst, words):
+            out = out.view(k * s, n_inst, words)
+        return self._rows_out(n, n_inst, out, k * s).view(k, s, n_inst, words)
 
     @classmethod
     def montecarlo_curve_shape(cls, n: int) -> Tuple[int, int, int]:

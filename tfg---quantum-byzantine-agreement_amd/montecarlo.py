@@ -48,6 +48,12 @@ dishonest commander splits the lieutenants, as a 32-bit word built by
 :func:`adversary` (presets in :data:`ADVERSARIES`).  :class:`AdversaryParty`
 is the definition; ``0xF`` is the reference's rule, and ``None`` (the default
 everywhere) calls exactly what was called before policies existed.
+
+A sweep (:func:`sweep`, ``Engine.montecarlo_sweep_sampled`` /
+``montecarlo_sweep_lists``) decides the instances of a
+curve under a whole grid of scenarios ``(n_dishonest, word)`` in the same one
+pass: the lists do not depend on either.  :func:`sweep_host` is its
+specification.
 """
 from __future__ import annotations
 
@@ -695,3 +701,60 @@ def curve(n: int, counts, n_dishonest: int, runs: int, seed: int, engine, batch:
     def decide(key, b, **into):
         return engine.montecarlo_curve_sampled(n, n_dishonest, key, b, counts, **into, **noise)
     return dict(zip(counts, _batches(n, len(counts), runs, batch, seed, engine, decide, tally, failures)))
+
+
+def _scenarios(n: int, scenarios) -> list:
+    """``scenarios`` as a list of ``(n_dishonest, checked policy word)``."""
+    try:
+        sc = [(int(k), word) for k, word in scenarios]
+    except (TypeError, ValueError):
+        raise QbaError("scenarios must be a sequence of (n_dishonest, policy word) pairs") from None
+    for i, (k, word) in enumerate(sc):
+        if not 0 <= k <= n:
+            raise QbaError(f"scenario {i}: n_dishonest={k} outside [0, {n}]")
+        sc[i] = (k, check_adversary(word))
+    return sc
+
+
+def sweep_host(n: int, counts, scenarios, n_inst: int, seed_base: int, engine, lists=None,
+               flip_q16: int = 0) -> np.ndarray:
+    """The specification of the sweep calls: the stack
+    of :func:`curve_host` under each scenario ``(n_dishonest, word)`` of
+    ``scenarios``, int32 [len(counts), len(scenarios), n_inst, out_words(n)].
+
+    Under one key the traitor draw is a partial Fisher-Yates
+    (:meth:`ProtocolRng.choice`): the traitors at k are the first k of the
+    traitors at k + 1.  Scenarios that differ in ``n_dishonest`` therefore run
+    on nested traitor sets, the same lists and the same commander's order."""
+    sc = _scenarios(n, scenarios)
+    rows = [curve_host(n, counts, k, n_inst, seed_base, engine, lists=lists, flip_q16=flip_q16, adversary=word)
+            for k, word in sc]
+    if not rows:
+        return np.zeros((len(list(counts)), 0, n_inst, out_words(n)), np.int32)
+    return np.stack(rows, axis=1)
+
+
+def sweep(n: int, counts, scenarios, runs: int, seed: int, engine, batch: int = 4096, tally: bool = False,
+          failures: int = 0, flip_q16: int = 0) -> dict:
+    """:func:`curve` under every scenario ``(n_dishonest, word)`` of
+    ``scenarios`` at once: ``runs`` instances, ``batch`` at a time as
+    :func:`run` keys them, each sampled and distilled once and decided at every
+    sizeL of ``counts`` under every scenario by one montecarlo_sweep_sampled
+    call per batch (at most 16 scenarios and 32 slices).  Returns ``{(sizeL,
+    n_dishonest, word): summary}`` in slice order, checkpoints outermost; each
+    summary is that of ``curve(..., n_dishonest, adversary=word)`` at that
+    sizeL.  ``tally``, ``failures`` and ``flip_q16`` as there.  Duplicate
+    scenarios would share a key: ValueError."""
+    counts = [int(c) for c in counts]
+    sc = _scenarios(n, scenarios)
+    if len(set(sc)) != len(sc):
+        raise ValueError("duplicate scenarios: every (n_dishonest, word) may be given once")
+    noise = {"flip_q16": _check_flip(flip_q16)} if flip_q16 else {}
+    engine._check_sweep(n, 0, counts, sc)  # before any device buffer: an empty grid has no slice
+    k = len(counts) * len(sc)
+
+    def decide(key, b, out=None):
+        into = {} if out is None else {"out": out}
+        return engine.montecarlo_sweep_sampled(n, key, b, counts, sc, **into, **noise).view(k, b, out_words(n))
+    keys = [(c, kd, word) for c in counts for kd, word in sc]
+    return dict(zip(keys, _batches(n, k, runs, batch, seed, engine, decide, tally, failures)))

@@ -48,6 +48,23 @@ def _sizes(text: str):
     return [int(float(x)) for x in text.split(",") if x.strip()]
 
 
+SWEEP_MAX = 16  # scenarios of one --sweep run (QBA_MC_SWEEP_MAX)
+
+
+def _scenarios(text: str, n_dishonest: int, montecarlo) -> list:
+    """--sweep's K:POLICY,... as [(K, policy word)]: a bare POLICY takes
+    ``n_dishonest``, a bare K the reference policy."""
+    out = []
+    for item in (x.strip() for x in text.split(",") if x.strip()):
+        k, sep, pol = item.partition(":")
+        if not sep:  # a decimal number is a traitor count; anything else a policy
+            k, pol = (k, "reference") if k.isdigit() else (str(n_dishonest), k)
+        out.append((int(k), montecarlo.parse_adversary(pol.strip())))
+    if len(set(out)) != len(out):
+        raise ValueError("a scenario is given twice")
+    return out
+
+
 def _args(argv):
     ap = argparse.ArgumentParser(prog="tfg", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -87,6 +104,11 @@ def _args(argv):
                     help="with --runs: the dishonest parties follow this policy, a preset (reference, relay, "
                          "reorder_low, mute, strip) or a policy word (montecarlo.adversary); the summary lines "
                          "end in adversary=0xWORD")
+    ap.add_argument("--sweep", default=None, metavar="K:POLICY,...",
+                    help="with --runs: decide every instance under each of these scenarios in one pass per batch "
+                         "(montecarlo.sweep; at most 16, and 32 lines with --curve): K traitors following POLICY "
+                         "(as --adversary takes it); a bare POLICY uses the positional nDishonest, a bare K the "
+                         "reference policy; one summary line per sizeL and scenario; implies --fused")
     ap.add_argument("--quiet", action="store_true", help="print only the outcome")
     ap.add_argument("--timing", action="store_true", help="print the wall time of the run")
     ap.add_argument("--wire", action="store_true",
@@ -124,6 +146,18 @@ def _args(argv):
             a.adversary = montecarlo.parse_adversary(a.adversary)
         except montecarlo.QbaError as e:
             ap.error(f"--adversary: {e}")
+    if a.sweep is not None:
+        if a.runs is None:
+            ap.error("--sweep needs --runs")
+        if a.adversary is not None or a.tables:
+            ap.error("--sweep: not with --adversary (name the policy per scenario) or --tables")
+        from . import montecarlo
+        try:
+            a.sweep = _scenarios(a.sweep, a.nDishonest, montecarlo)
+        except (ValueError, montecarlo.QbaError) as e:
+            ap.error(f"--sweep: {e}")
+        if not 1 <= len(a.sweep) <= SWEEP_MAX or len(a.sweep) * len(a.curve or [0]) > CURVE_MAX:
+            ap.error(f"--sweep: between 1 and {SWEEP_MAX} scenarios, and at most {CURVE_MAX} lines with --curve")
     return a
 
 
@@ -239,7 +273,8 @@ def _torchrun(a, size_l, verbose, log) -> int:
 def _montecarlo(a, eng, size_l) -> int:
     """--runs R: R independent count-mode instances decided on the device
     (montecarlo.run); one summary line, or with --curve one per sizeL
-    (montecarlo.curve)."""
+    (montecarlo.curve), or with --sweep one per sizeL and scenario
+    (montecarlo.sweep), each the line of the --adversary run of that scenario."""
     from . import montecarlo
     seed = secrets.randbits(62) if a.seed is None else a.seed
     t0 = time.perf_counter()
@@ -250,15 +285,20 @@ def _montecarlo(a, eng, size_l) -> int:
     if a.adversary is not None:
         how["adversary"] = a.adversary
         noise += f" adversary={a.adversary:#x}"
-    if a.curve is not None:
+    if a.sweep is not None:
+        grid = montecarlo.sweep(a.parties, a.curve if a.curve is not None else [size_l], a.sweep, a.runs, seed, eng,
+                                batch=a.batch, **how)
+        points = {(c, k, f"{noise} adversary={word:#x}"): s for (c, k, word), s in grid.items()}
+    elif a.curve is not None:
         points = montecarlo.curve(a.parties, a.curve, a.nDishonest, a.runs, seed, eng, batch=a.batch, **how)
     else:
         points = {size_l: montecarlo.run(a.parties, size_l, a.nDishonest, a.runs, seed, eng, batch=a.batch,
                                          path="tables_noisy" if a.tables else "fused" if a.fused else "tables",
                                          **how)}
     for c, s in points.items():
+        c, dis, tail = c if a.sweep is not None else (c, a.nDishonest, noise)
         print(f"Runs: {s['runs']} Successes: {s['successes']} Rate: {s['rate']:.6f} "
-              f"(n={a.parties}, sizeL={c}, dishonest={a.nDishonest}, empty-V_i runs={s['empty_vi_runs']}){noise}")
+              f"(n={a.parties}, sizeL={c}, dishonest={dis}, empty-V_i runs={s['empty_vi_runs']}){tail}")
         if a.failures:
             print(f"Failed runs ({len(s['failed_runs'])} of {s['failed_total']}, key = seed + index, seed={seed}): "
                   + " ".join(str(i) for i in s["failed_runs"]))

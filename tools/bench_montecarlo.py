@@ -46,6 +46,13 @@ instances x n = 7 x sizeL = 1e5, 2 dishonest, on one GPU.
       and again last in the same session.  Other policies run another protocol:
       their times are reported without a verdict.
 
+  --sweep K:POLICY,...  (repeatable) another mode, per --sizeL and per --curve:
+      one montecarlo_sweep_sampled call over the grid of scenarios (K traitors
+      under POLICY; a bare POLICY takes --dishonest, a bare K the reference
+      policy) against the S montecarlo_curve_sampled calls with adversary= of
+      the same grid, the S timed as one interval; the rows of the two are
+      compared at the timed shape.  One JSON line per --sweep and shape.
+
 (a), (b), (d), the --tally calls, the --flip calls and the --curve pair are device-event times of single calls on warm code: median, min
 and max over --repeats launches after --warmup launches.  (c) is host wall
 time around runs that end in device synchronisation (each reads its tables
@@ -105,14 +112,22 @@ def main(argv=None) -> int:
     ap.add_argument("--adversary", action="append", default=None, metavar="NAME|0xHEX",
                     help="time montecarlo_sampled through the policy entry point at 0xF and at each policy given, "
                          "beside the call without a policy, at each --sizeL; repeatable; nothing else is measured")
+    ap.add_argument("--sweep", action="append", default=None, metavar="K:POLICY,...",
+                    help="time one sweep call over these scenarios against the separate curve calls with a policy, "
+                         "at each --sizeL (one checkpoint) or each --curve; repeatable; nothing else is measured")
     a = ap.parse_args(argv)
+    if a.sweep and (a.flip or a.tally or a.tables or a.adversary):
+        ap.error("--sweep goes with --sizeL or --curve alone")
     if a.adversary and (a.flip or a.curve or a.tally or a.tables):
         ap.error("--adversary goes with --sizeL alone")
     if a.tables and (not a.flip or a.curve or a.tally):
         ap.error("--tables needs --flip and goes with neither --curve nor --tally")
 
     eng = importlib.import_module(f"{PKG}.engine").Engine(0)
-    if a.adversary:
+    if a.sweep:
+        shapes = [[s] for s in (a.sizeL or [])] + [sorted({int(c) for c in text.split(",")}) for text in a.curve or []]
+        lines = [json.dumps(_measure_sweep(a, eng, counts, text)) for text in a.sweep for counts in shapes or [[100_000]]]
+    elif a.adversary:
         lines = [json.dumps(_measure_adversary(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
     elif a.tables:
         lines = [json.dumps(_measure_flip_tables(a, eng, size_l, k)) for size_l in (a.sizeL or [100_000])
@@ -161,6 +176,42 @@ def _measure_curve(a, eng, counts) -> dict:
     res["separate_over_curve_at_median"] = s["median_ms"] / c["median_ms"]
     # faster only where the min-max ranges do not overlap
     res["curve_faster"] = c["max_ms"] < s["min_ms"]
+    res["separate_faster"] = s["max_ms"] < c["min_ms"]
+    return res
+
+
+def _measure_sweep(a, eng, counts, text) -> dict:
+    """--sweep: one sweep call against the separate policy curve calls of its grid."""
+    import torch
+    tfg = importlib.import_module(f"{PKG}.tfg")
+    mc = importlib.import_module(f"{PKG}.montecarlo")
+    n, inst = a.parties, a.instances
+    scen = tfg._scenarios(text, a.dishonest, mc)
+    sweep = eng.montecarlo_sweep_sampled(n, a.seed, inst, counts, scen)
+    single = torch.empty((len(scen), len(counts), inst, sweep.shape[-1]), dtype=torch.int32, device=eng.device)
+
+    def separate():
+        for s, (k, word) in enumerate(scen):
+            eng.montecarlo_curve_sampled(n, k, a.seed, inst, counts, single[s], adversary=word)
+
+    def equal():
+        return bool(torch.equal(sweep, single.transpose(0, 1)))
+
+    separate()
+    torch.cuda.synchronize()
+    res = {"config": {"n": n, "counts": counts, "scenarios": [[k, f"{word:#x}"] for k, word in scen],
+                      "instances": inst, "seed": a.seed, "device": torch.cuda.get_device_name(0),
+                      "slices": len(counts) * len(scen), "entries_sweep": counts[-1],
+                      "entries_separate": counts[-1] * len(scen)},
+           "rows_equal_separate_calls": equal()}
+    res["separate_montecarlo_curve_sampled_adv"] = _events(separate, a.warmup, a.repeats)
+    res["sweep_montecarlo_sweep_sampled"] = _events(
+        lambda: eng.montecarlo_sweep_sampled(n, a.seed, inst, counts, scen, sweep), a.warmup, a.repeats)
+    res["rows_equal_separate_calls"] = res["rows_equal_separate_calls"] and equal()
+    s, c = res["separate_montecarlo_curve_sampled_adv"], res["sweep_montecarlo_sweep_sampled"]
+    res["separate_over_sweep_at_median"] = s["median_ms"] / c["median_ms"]
+    # faster only where the min-max ranges do not overlap
+    res["sweep_faster"] = c["max_ms"] < s["min_ms"]
     res["separate_faster"] = s["max_ms"] < c["min_ms"]
     return res
 
