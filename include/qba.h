@@ -511,6 +511,71 @@ QBA_API int qba_montecarlo_tally(qba_ctx *ctx, int n_parties, const int32_t *row
                                  int64_t *tally_dev, int select, int64_t *capture_dev,
                                  int64_t capture_cap, qba_stream stream);
 
+/* A transcript of chosen runs.  The two calls re-run
+ * the instances keyed seed_base + idx_dev[j] (mod 2^64), j in [0, n_idx), as
+ * qba_montecarlo_sampled_adv / qba_montecarlo_lists_adv decide them (the lists
+ * form: slot j reads lists_dev + j * inst_stride, and flip_q16 flips its
+ * entries as the sampled form's) and write per slot j
+ *   rows_dev   + j * (4 + 5*(n+1))        the result row, word for word the
+ *                                         decision call's for that key
+ *   counts_dev + j * (n+1)                int32: the events rank r = 0..n
+ *                                         produced (rank 0: none)
+ *   events_dev + ((j * (n+1) + r) * cap) * 2   uint32 {head, pkt}: the first
+ *                                         min(count, cap) events of rank r, in
+ *                                         the order the rank produced them
+ * and nothing else: events past `cap` are counted, not stored.  A row with a
+ * nonzero status has counts 0.
+ *   head = kind [0:3) | round [3:8) | peer [8:12) | slot [12:17) | code [17:21)
+ *          | len [21:26), every other bit 0; round 0 is the commander's epoch
+ *   QBA_EV_RECV    a packet a lieutenant processes (the commander's: peer 1,
+ *                  slot 0, round 0; then every mailbox packet of the rounds):
+ *                  peer the source, slot the mailbox slot read, len the lists
+ *                  after the own tuple joined, code 0 accepted and v added to
+ *                  V_i; 1, 2, 3 the first of Cond1, Cond2, Cond3 (tfg.py:87-98)
+ *                  that fails; 4 consistent but v already in V_i; 5 consistent
+ *                  and new but len != round + 1.  Codes 0, 4, 5 are the row's
+ *                  accept, codes 1-3 its reject.
+ *   QBA_EV_SEND    a destination a broadcast visits, the commander's n - 1
+ *                  sends included (round 0): peer the destination, code the
+ *                  drawn action 0..4 or QBA_EV_HONEST, len the lists of the
+ *                  packet sent, slot the mailbox slot written,
+ *                  QBA_EV_SLOT_MUTED for a send action 0 suppressed,
+ *                  QBA_EV_SLOT_FULL for one dropped on a full mailbox.  Events
+ *                  with slot < 30 are the row's sent.
+ *   QBA_EV_DECIDE  the last event of every rank 1..n: pkt the decision as
+ *                  uint32, len popcount(V_i)
+ *   pkt (RECV: as read; SEND: after the traitor's mutation) = v [0:4) | P's u
+ *   [4:8) | P cleared [8] | the tuples' u [9:13) | an empty tuple present [13] |
+ *   mask of the tuples' representatives [16:32), with P's u zero under the
+ *   cleared bit and the tuples' u zero under an empty mask.
+ * n_match_dev (NULL: none): a device int64; slot j does nothing when j >=
+ * min(n_idx, *n_match_dev), read when the kernel runs -- a tally's capture row
+ * and its word 10 feed the call with no host round trip.
+ * Checked in this order, each QBA_EINVAL: n_parties; count < 2^31; flip_q16 <=
+ * 65535; n_dishonest in [0, n_parties]; adv as the _adv calls check it; n_idx
+ * >= 0 and idx_dev not NULL when n_idx > 0; 1 <= cap <= QBA_TRACE_CAP_MAX;
+ * rows_dev, counts_dev, events_dev not NULL when n_idx > 0; ctx; then (lists
+ * form) lists_dev, ld and inst_stride as qba_montecarlo_lists.  Asynchronous on
+ * `stream`, allocate and copy nothing, legal in a stream capture.  The launch
+ * shape of the sampled form is qba_montecarlo_shape's.  Specification:
+ * montecarlo.trace_host. */
+#define QBA_EV_RECV 1u
+#define QBA_EV_SEND 2u
+#define QBA_EV_DECIDE 3u
+#define QBA_EV_HONEST 7u
+#define QBA_EV_SLOT_FULL 30u
+#define QBA_EV_SLOT_MUTED 31u
+#define QBA_TRACE_CAP_MAX 4096
+QBA_API int qba_montecarlo_trace_sampled(qba_ctx *ctx, int n_parties, uint64_t seed_base, const int64_t *idx_dev,
+                                         int64_t n_idx, const int64_t *n_match_dev, uint64_t count, int n_dishonest,
+                                         uint32_t adv, uint32_t flip_q16, int64_t cap, int32_t *rows_dev,
+                                         int32_t *counts_dev, uint32_t *events_dev, qba_stream stream);
+QBA_API int qba_montecarlo_trace_lists(qba_ctx *ctx, int n_parties, uint64_t seed_base, const int64_t *idx_dev,
+                                       int64_t n_idx, const int64_t *n_match_dev, uint64_t count, int n_dishonest,
+                                       uint32_t adv, uint32_t flip_q16, int64_t cap, const uint8_t *lists_dev,
+                                       uint64_t ld, uint64_t inst_stride, int32_t *rows_dev, int32_t *counts_dev,
+                                       uint32_t *events_dev, qba_stream stream);
+
 /* ---- (A5-A8) checks, exact-order mode (bit-exact protocol parity) --------------- */
 /* isQCorrList = {k : Li[k] != Lc[k]} (tfg.py:327) as ascending indices.
  * *count_host receives the number found; at most `cap` are written. Synchronous. */

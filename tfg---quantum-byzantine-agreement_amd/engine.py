@@ -620,6 +620,76 @@ class Engine:
              int(select), _ptr(capture) if cap else None, cap, self.stream())
         return tally
 
+    # -- a transcript of chosen runs (qba_montecarlo_trace_*) --
+    TRACE_CAP_MAX = 4096  # QBA_TRACE_CAP_MAX
+
+    def _trace_args(self, n: int, n_dishonest: int, indices, count: int, flip_q16: int, adversary, cap: int,
+                    n_match, out):
+        """The checks the two montecarlo_trace_* methods share: ``(idx, n_idx,
+        n_match, flip, word, (rows, counts, events))`` with the three outputs
+        allocated when ``out`` is None."""
+        self._check_n(n)
+        self._check_curve(n, n_dishonest, 0, [count])
+        flip = self._check_flip(flip_q16)
+        adv = self._check_adversary(0xF if adversary is None else adversary)
+        if not 1 <= int(cap) <= self.TRACE_CAP_MAX:
+            raise QbaError(f"cap must be in [1, {self.TRACE_CAP_MAX}]")
+        if not isinstance(indices, torch.Tensor):  # host indices: reduced mod 2^64 into the int64 the kernel adds
+            host = np.array([int(i) & (2**64 - 1) for i in indices], dtype=np.uint64).view(np.int64)
+            indices = torch.from_numpy(host).to(self.device)
+        if indices.dtype != torch.int64 or indices.dim() != 1 or not indices.is_contiguous() or \
+                indices.device != self.device:
+            raise QbaError("indices must be a contiguous int64 [n_idx] device tensor (or host integers)")
+        if n_match is not None and (not isinstance(n_match, torch.Tensor) or n_match.dtype != torch.int64 or
+                                    n_match.numel() != 1 or n_match.device != self.device):
+            raise QbaError("n_match must be a one-element int64 device tensor")
+        n_idx, g = indices.shape[0], n + 1
+        shapes = ((n_idx, 4 + 5 * g), (n_idx, g), (n_idx, g, int(cap), 2))
+        if out is None:
+            out = tuple(torch.zeros(s, dtype=torch.int32, device=self.device) for s in shapes)
+        if len(out) != 3 or any(not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != s or
+                                not t.is_contiguous() or t.device != self.device for t, s in zip(out, shapes)):
+            raise QbaError(f"out must be three contiguous int32 device tensors of shapes {shapes}")
+        return indices, n_idx, n_match, flip, adv, tuple(out)
+
+    def montecarlo_trace_sampled(self, n: int, n_dishonest: int, seed_base: int, indices, count: int, cap: int = 256,
+                                 flip_q16: int = 0, adversary: Optional[int] = None,
+                                 n_match: Optional[torch.Tensor] = None, out=None):
+        """Re-run the instances keyed ``seed_base + indices[j]`` of
+        montecarlo_sampled(..., flip_q16=, adversary=) with a transcript of
+        their rounds (qba_montecarlo_trace_sampled): ``(rows, counts, events)``,
+        int32 [n_idx, 4 + 5*(n+1)], [n_idx, n+1] and [n_idx, n+1, cap, 2] --
+        the row of that key, how many events each rank produced, and the first
+        ``cap`` of them as {head, pkt} bit patterns (montecarlo.EV_*,
+        montecarlo.format_trace).  ``indices``: an int64 device tensor -- a
+        tally's capture row as it lies -- or host integers.  ``n_match``: a
+        one-element int64 device tensor (a tally's word T_CAPTURE); slots from
+        ``min(n_idx, n_match)`` on are left untouched.  ``out``: the three
+        tensors to write (new zeroed ones when None)."""
+        idx, n_idx, n_match, flip, adv, out = self._trace_args(n, n_dishonest, indices, count, flip_q16, adversary,
+                                                               cap, n_match, out)
+        self.prepare(n)
+        call("qba_montecarlo_trace_sampled", self.ctx, n, _u64(seed_base), _ptr(idx), n_idx,
+             None if n_match is None else _ptr(n_match), count, n_dishonest, adv, flip, int(cap), _ptr(out[0]),
+             _ptr(out[1]), _ptr(out[2]), self.stream())
+        return out
+
+    def montecarlo_trace_lists(self, n: int, n_dishonest: int, seed_base: int, indices, lists, count: int,
+                               cap: int = 256, flip_q16: int = 0, adversary: Optional[int] = None,
+                               n_match: Optional[torch.Tensor] = None, out=None):
+        """The same from injected lists (qba_montecarlo_trace_lists), uint8
+        [n_idx, n+1, >= count] as montecarlo_lists takes them: ``lists[j]``
+        belongs to ``indices[j]``."""
+        idx, n_idx, n_match, flip, adv, out = self._trace_args(n, n_dishonest, indices, count, flip_q16, adversary,
+                                                               cap, n_match, out)
+        lists, n_lists, ld, stride = self._mc_lists(n, lists, count)
+        if n_lists != n_idx:
+            raise QbaError(f"lists holds {n_lists} instances for {n_idx} indices")
+        call("qba_montecarlo_trace_lists", self.ctx, n, _u64(seed_base), _ptr(idx), n_idx,
+             None if n_match is None else _ptr(n_match), count, n_dishonest, adv, flip, int(cap), _ptr(lists), ld,
+             stride, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), self.stream())
+        return out
+
     # -- (A5-A8) count mode -------------------------------------------------------
     def check_counts(self, lists: torch.Tensor, n: int, count: int,
                      counts: Optional[Counts] = None, accumulate: bool = False) -> Counts:

@@ -510,7 +510,8 @@ def summary_from_tally(n: int, tally_row) -> dict:
             "sent": t[T_SENT]}
 
 
-def _batches(n: int, k: int, runs: int, batch: int, seed: int, engine, decide, tally: bool, failures: int) -> list:
+def _batches(n: int, k: int, runs: int, batch: int, seed: int, engine, decide, tally: bool, failures: int,
+             explain=None) -> list:
     """The summaries of the ``k`` slices of ``runs`` instances decided ``batch``
     at a time, the batch at offset ``off`` under key ``seed + off``:
     ``decide(key, b)`` returns the rows of the b instances from ``key`` on,
@@ -521,7 +522,15 @@ def _batches(n: int, k: int, runs: int, batch: int, seed: int, engine, decide, t
     buffer) are joined on the host and go through :func:`summarize`.  Otherwise
     they are tallied on the device: one row buffer of ``batch`` instances
     serves every batch, and only the [k, 32] tally (and the [k, failures]
-    captured indices) come to the host, for :func:`summary_from_tally`."""
+    captured indices) come to the host, for :func:`summary_from_tally`.
+
+    ``explain`` (with ``failures``): ``(slices, flip_q16, cap)``, ``slices[j]``
+    the ``(sizeL, n_dishonest, word)`` of slice j.  After the last batch one
+    montecarlo_trace_sampled call per slice re-runs that slice's captured
+    failures, fed by its capture row and match count as they lie on the device;
+    the tally, the indices and the transcripts then come to the host together,
+    and every summary gets ``trace`` = (rows, counts, events) in the order of
+    ``failed_runs``."""
     import torch
     if runs < 0 or batch < 1:
         raise ValueError("runs >= 0 and batch >= 1")
@@ -541,13 +550,23 @@ def _batches(n: int, k: int, runs: int, batch: int, seed: int, engine, decide, t
         out = buf[:k * b * words].view(k, b, words)
         decide(key, b, out=out)
         engine.montecarlo_tally(n, out, tal, inst_base=off, select=SEL_FAILED if failures else 0, capture=capture)
-    host = tal.cpu().numpy()
+    traces = []
+    if explain and failures:
+        slices, flip, ev_cap = explain
+        for j, (c, kd, word) in enumerate(slices):
+            traces.append(engine.montecarlo_trace_sampled(n, kd, seed, capture[j], c, cap=ev_cap, flip_q16=flip,
+                                                          adversary=word, n_match=tal[j, T_CAPTURE:T_CAPTURE + 1]))
+    host = tal.cpu().numpy()  # the one synchronisation: every launch above is done when it returns
     res = [summary_from_tally(n, row) for row in host]
     if failures:
         cap = capture.cpu().numpy()
         for j, s in enumerate(res):
             s["failed_total"] = int(host[j, T_CAPTURE])
-            s["failed_runs"] = sorted(int(i) for i in cap[j, :min(failures, s["failed_total"])])
+            got = cap[j, :min(failures, s["failed_total"])]
+            s["failed_runs"] = sorted(int(i) for i in got)
+            if traces:
+                order = np.argsort(got, kind="stable")
+                s["trace"] = tuple(t.cpu().numpy()[order] for t in traces[j])
     return res
 
 
@@ -617,7 +636,7 @@ def masks_from_lists(n: int, lists) -> dict:
 
 def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, packed: bool = True,
         batch: int = 4096, path: str = "tables", tally: bool = False, failures: int = 0, flip_q16: int = 0,
-        adversary: Optional[int] = None) -> dict:
+        adversary: Optional[int] = None, explain: int = 0) -> dict:
     """``runs`` independent instances on the device, ``batch`` at a time, batch
     at offset ``off`` under key ``seed + off``; only the result rows are copied
     to the host.  Returns :func:`summarize` of all rows.
@@ -642,7 +661,13 @@ def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, pack
     with ``flip_q16=0`` it is ``"tables"``.
 
     ``adversary=word`` (any path): the dishonest parties follow that policy
-    (:func:`adversary`); the decisions go through the ``_adv`` kernels."""
+    (:func:`adversary`); the decisions go through the ``_adv`` kernels.
+
+    ``explain=cap > 0`` (with ``failures``): adds ``trace``, the device
+    transcripts ``(rows, counts, events)`` of ``failed_runs`` with at most
+    ``cap`` stored events per rank (``Engine.montecarlo_trace_sampled``, fed
+    from the capture buffer on the device; :func:`format_trace` renders one).
+    Every path's rows are equal, so the fused trace explains them all."""
     if path not in ("tables", "fused", "tables_noisy"):
         raise ValueError("path is 'tables', 'fused' or 'tables_noisy'")
     noise = {"flip_q16": _check_flip(flip_q16)} if flip_q16 else {}
@@ -661,7 +686,8 @@ def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, pack
         if lists is None:
             lists = buf
         return engine.protocol_batched(n, n_dishonest, key, counts, **into, **adv)
-    return _batches(n, 1, runs, batch, seed, engine, decide, tally, failures)[0]
+    ex = ([(sizeL, n_dishonest, adversary)], flip_q16, explain) if explain else None
+    return _batches(n, 1, runs, batch, seed, engine, decide, tally, failures, ex)[0]
 
 
 def curve_host(n: int, counts, n_dishonest: int, n_inst: int, seed_base: int, engine, lists=None,
@@ -683,14 +709,14 @@ def curve_host(n: int, counts, n_dishonest: int, n_inst: int, seed_base: int, en
 
 
 def curve(n: int, counts, n_dishonest: int, runs: int, seed: int, engine, batch: int = 4096, tally: bool = False,
-          failures: int = 0, flip_q16: int = 0, adversary: Optional[int] = None) -> dict:
+          failures: int = 0, flip_q16: int = 0, adversary: Optional[int] = None, explain: int = 0) -> dict:
     """The failure curve over sizeL: ``runs`` instances, ``batch`` at a time as
     :func:`run` keys them, each decided at every sizeL of the strictly
     increasing ``counts`` by one montecarlo_curve_sampled call per batch.
     Returns ``{sizeL: summarize(...)}`` in checkpoint order; the summary at
     sizeL = c is that of ``run(n, c, ..., path="fused")``.  ``tally`` and
-    ``failures`` as in :func:`run`, per checkpoint; ``flip_q16`` and
-    ``adversary`` as there."""
+    ``failures`` as in :func:`run`, per checkpoint; ``flip_q16``,
+    ``adversary`` and ``explain`` as there (one trace call per checkpoint)."""
     counts = [int(c) for c in counts]
     noise = {"flip_q16": _check_flip(flip_q16)} if flip_q16 else {}
     if adversary is not None:
@@ -700,7 +726,8 @@ def curve(n: int, counts, n_dishonest: int, runs: int, seed: int, engine, batch:
 
     def decide(key, b, **into):
         return engine.montecarlo_curve_sampled(n, n_dishonest, key, b, counts, **into, **noise)
-    return dict(zip(counts, _batches(n, len(counts), runs, batch, seed, engine, decide, tally, failures)))
+    ex = ([(c, n_dishonest, adversary) for c in counts], flip_q16, explain) if explain else None
+    return dict(zip(counts, _batches(n, len(counts), runs, batch, seed, engine, decide, tally, failures, ex)))
 
 
 def _scenarios(n: int, scenarios) -> list:
@@ -735,7 +762,7 @@ def sweep_host(n: int, counts, scenarios, n_inst: int, seed_base: int, engine, l
 
 
 def sweep(n: int, counts, scenarios, runs: int, seed: int, engine, batch: int = 4096, tally: bool = False,
-          failures: int = 0, flip_q16: int = 0) -> dict:
+          failures: int = 0, flip_q16: int = 0, explain: int = 0) -> dict:
     """:func:`curve` under every scenario ``(n_dishonest, word)`` of
     ``scenarios`` at once: ``runs`` instances, ``batch`` at a time as
     :func:`run` keys them, each sampled and distilled once and decided at every
@@ -743,8 +770,8 @@ def sweep(n: int, counts, scenarios, runs: int, seed: int, engine, batch: int = 
     call per batch (at most 16 scenarios and 32 slices).  Returns ``{(sizeL,
     n_dishonest, word): summary}`` in slice order, checkpoints outermost; each
     summary is that of ``curve(..., n_dishonest, adversary=word)`` at that
-    sizeL.  ``tally``, ``failures`` and ``flip_q16`` as there.  Duplicate
-    scenarios would share a key: ValueError."""
+    sizeL.  ``tally``, ``failures``, ``flip_q16`` and ``explain`` as there (one
+    trace call per slice).  Duplicate scenarios would share a key: ValueError."""
     counts = [int(c) for c in counts]
     sc = _scenarios(n, scenarios)
     if len(set(sc)) != len(sc):
@@ -753,8 +780,226 @@ def sweep(n: int, counts, scenarios, runs: int, seed: int, engine, batch: int = 
     engine._check_sweep(n, 0, counts, sc)  # before any device buffer: an empty grid has no slice
     k = len(counts) * len(sc)
 
+    keys = [(c, kd, word) for c in counts for kd, word in sc]
+
     def decide(key, b, out=None):
         into = {} if out is None else {"out": out}
         return engine.montecarlo_sweep_sampled(n, key, b, counts, sc, **into, **noise).view(k, b, out_words(n))
-    keys = [(c, kd, word) for c in counts for kd, word in sc]
-    return dict(zip(keys, _batches(n, k, runs, batch, seed, engine, decide, tally, failures)))
+    ex = (keys, flip_q16, explain) if explain else None
+    return dict(zip(keys, _batches(n, k, runs, batch, seed, engine, decide, tally, failures, ex)))
+
+
+# ---------------------------------------------------------------------------
+# The transcript of a run
+# ---------------------------------------------------------------------------
+EV_RECV, EV_SEND, EV_DECIDE = 1, 2, 3
+EV_HONEST = 7                       # SEND code of an honest sender
+EV_SLOT_FULL, EV_SLOT_MUTED = 30, 31
+TRACE_CAP_MAX = 4096
+PKT_CLEARED, PKT_EMPTY = 1 << 8, 1 << 13
+VERDICTS = ("accepted", "Cond1", "Cond2", "Cond3", "known v", "wrong length")
+ACTIONS = ("maybe not send", "replace the order", "clear P", "clear L", "relay")
+
+
+def event_head(kind: int, rnd: int = 0, peer: int = 0, slot: int = 0, code: int = 0, length: int = 0) -> int:
+    """kind [0:3) | round [3:8) | peer [8:12) | slot [12:17) | code [17:21) | len [21:26)"""
+    return kind | rnd << 3 | peer << 8 | slot << 12 | code << 17 | length << 21
+
+
+def event_fields(head: int) -> dict:
+    h = int(head) & _U32
+    return {"kind": h & 7, "round": (h >> 3) & 31, "peer": (h >> 8) & 15, "slot": (h >> 12) & 31,
+            "code": (h >> 17) & 15, "len": (h >> 21) & 31}
+
+
+def packet_word(P, v, L) -> int:
+    """The packet (P, v, L) of a CountParty as the 32-bit word of the decision
+    kernels (csrc/qba_proto_rounds.h), in the form the events carry: v [0:4) |
+    P's u [4:8) | P cleared [8] | the tuples' u [9:13) | an empty tuple present
+    [13] | mask of the tuples' representatives [16:32); P's u is 0 under the
+    cleared bit and the tuples' u is 0 when no tuple is left."""
+    descs = [d for d in L if d != ()]
+    mask = 0
+    for _, rep in descs:
+        mask |= 1 << rep
+    cleared = P.u is None
+    return (int(v) | (0 if cleared else int(P.u) << 4) | (PKT_CLEARED if cleared else 0) |
+            ((descs[0][0] << 9) if descs else 0) | (PKT_EMPTY if () in L else 0) | mask << 16)
+
+
+class TraceParty(AdversaryParty):
+    """AdversaryParty that writes down what it does: ``events``, the list of
+    ``(head, pkt)`` of its rank in the order of its own calls, which is the
+    order of the lane's loop in the trace kernels.  The verdict of a received
+    packet comes from Cond1, Cond2 and Cond3 evaluated in order on the same
+    CountTables, and its boolean is asserted against ``consistent``'s."""
+
+    sink = None  # {rank: party} of the run, set on the subclass trace_host makes
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.events = []
+        self._rnd = 0          # 0: the commander's epoch
+        self._inbox = []       # (source, slot, word) of the drained, unprocessed packets
+        self._slots = (None, {})  # the round the send slots belong to, {dest: sends so far}
+        if self.sink is not None:
+            self.sink[self.rank] = self
+
+    def _put(self, kind, peer, slot, code, length, pkt):
+        self.events.append((event_head(kind, self._rnd, peer, slot, code, length), int(pkt) & _U32))
+
+    def verdict(self, v, L) -> int:
+        """0, or the first of Cond1, Cond2, Cond3 (tfg.py:87-98) that fails."""
+        t = self.tables
+        if len({t.length(d) for d in L}) != 1:
+            return 1
+        descs = [d for d in L if d != ()]
+        if any(t.H[u, g, int(v)] != 0 for u, g in descs):
+            return 2
+        if any(t.C[a[0], a[1], b[1]] != 0 for i, a in enumerate(descs) for b in descs[i + 1:]):
+            return 3
+        return 0
+
+    def recv(self, src):
+        P, v, L = super().recv(src)
+        self._inbox.append((src, sum(1 for s, _, _ in self._inbox if s == src), packet_word(P, v, L)))
+        return P, v, L
+
+    def add_own_and_check(self, P, v, L, pre=None) -> bool:
+        src, slot, word = self._inbox.pop(0)
+        L.add(self.own_tuple(P))
+        code = self.verdict(v, L)
+        ok = code == 0
+        assert ok == self.tables.consistent(v, L), "the verdict and consistent() disagree"
+        self._tally(ok)
+        if ok:  # what lieu_receive tests next (epoch 0: V_i is empty and the one list is the own)
+            code = 4 if v in self.Vi else 5 if len(L) != self._rnd + 1 else 0
+        self._put(EV_RECV, src, slot, code, len(L), word)
+        return ok
+
+    def lieu_receive(self, P, v, L, rnd, pre=None):
+        self._rnd = rnd
+        super().lieu_receive(P, v, L, rnd, pre)
+
+    def send(self, dest, P, v, L):
+        if self.rank == 1:
+            self._put(EV_SEND, dest, 0, EV_HONEST, len(L), packet_word(P, v, L))
+        super().send(dest, P, v, L)
+
+    def lieu_broadcast(self, P, v, L):
+        """AdversaryParty.lieu_broadcast, draw for draw, with a SEND event per
+        destination (trace_host's rows are held to run_host's)."""
+        acts = [a for a in range(5) if (self.adv >> a) & 1]
+        order, fresh = (self.adv >> 8) & 3, (self.adv >> 12) & 1
+        if self._slots[0] != self._rnd:
+            self._slots = (self._rnd, {})
+        P0, v0, L0 = P, v, L
+        for dest in range(2, self.n + 1):
+            if dest == self.rank:
+                continue
+            go, action = 1, EV_HONEST
+            if self.dishonest:
+                if fresh:
+                    P, v, L = copy.copy(P0), v0, set(L0)
+                action = acts[self.rng.randint(len(acts))]
+                if action == ACT_MUTE:
+                    go = self.rng.randint(2)
+                elif action == ACT_REORDER:
+                    if order == ORDER_LOW:
+                        v = 1 if int(v) == 0 else 0
+                    else:
+                        v = self.rng.randint(self.n + 1 if order == ORDER_REFERENCE else self.w)
+                elif action == ACT_CLEAR_P:
+                    P.clear()
+                elif action == ACT_CLEAR_L:
+                    L.clear()
+            slot = EV_SLOT_MUTED
+            if go:
+                k = self._slots[1].get(dest, 0)
+                self._slots[1][dest] = k + 1
+                slot = k if k < self.w else EV_SLOT_FULL
+                self.send(dest, P, v, L)
+            self._put(EV_SEND, dest, slot, action, len(L), packet_word(P, v, L))
+
+
+def trace_host(n: int, sizeL: int, n_dishonest: int, indices, seed_base: int, engine, lists=None,
+               flip_q16: int = 0, adversary: Optional[int] = None):
+    """The specification of the trace calls: :func:`run_host` of the instance
+    keyed ``seed_base + i`` for every i of ``indices`` (``lists[j]`` belongs to
+    ``indices[j]``) with :class:`TraceParty` at the ``party_cls`` seam.  Returns
+    ``(rows, counts, events)``: int32 [k, out_words(n)], int32 [k, n+1] and, per
+    index and rank 0..n, the whole list of ``(head, pkt)`` -- the device keeps
+    the first ``cap`` of each.  An instance with a nonzero status has no events."""
+    word = check_adversary(ADV_REFERENCE if adversary is None else adversary)
+    indices = [int(i) for i in indices]
+    rows = np.zeros((len(indices), out_words(n)), np.int32)
+    counts = np.zeros((len(indices), n + 1), np.int32)
+    events = []
+    for j, i in enumerate(indices):
+        sink: Dict[int, TraceParty] = {}
+        cls = type(f"TraceParty_{word:x}", (TraceParty,), {"adv": word, "sink": sink})
+        rows[j] = run_host(n, sizeL, n_dishonest, 1, (int(seed_base) + i) & MASK64, engine,
+                           lists=None if lists is None else np.asarray(lists)[j:j + 1], party_cls=cls,
+                           flip_q16=flip_q16)[0]
+        per_rank = [[] for _ in range(n + 1)]
+        if rows[j, 3] == 0:
+            for r in range(1, n + 1):
+                dec, vi = int(rows[j, 4 + 5 * r]), int(rows[j, 5 + 5 * r])
+                per_rank[r] = sink[r].events + [(event_head(EV_DECIDE, length=bin(vi).count("1")), dec & _U32)]
+        counts[j] = [len(e) for e in per_rank]
+        events.append(per_rank)
+    return rows, counts, events
+
+
+def trace_events(counts, events, j: int = 0) -> list:
+    """Slot ``j`` of a device trace (int32 or uint32 arrays of
+    ``Engine.montecarlo_trace_*``, on the host) as :func:`trace_host` lays its
+    events out: per rank 0..n the stored ``(head, pkt)``, the first ``min(count,
+    cap)`` of them."""
+    ev = np.asarray(events[j]).view(np.uint32) if np.asarray(events[j]).dtype == np.int32 else np.asarray(events[j])
+    return [[(int(h), int(p)) for h, p in ev[r, :min(int(c), ev.shape[1])]]
+            for r, c in enumerate(np.asarray(counts[j]))]
+
+
+def _bits(mask: int) -> list:
+    return [b for b in range(32) if (int(mask) >> b) & 1]
+
+
+def _packet_text(pkt: int, length: int) -> str:
+    p = "P cleared, " if pkt & PKT_CLEARED else ""
+    return f"v={pkt & 15}, {p}{length} list{'' if length == 1 else 's'}"
+
+
+def format_trace(n: int, row, counts, events) -> str:
+    """One instance's transcript as text, a line per event in the spirit of the
+    reference's log, rank by rank: ``row`` its result row, ``counts`` [n+1] and
+    ``events`` per rank the stored ``(head, pkt)`` (a list per rank, or the
+    [n+1, cap, 2] array of a device trace).  ``B`` marks a dishonest rank.
+    Events that were counted and not stored are reported as a count."""
+    row = [int(x) for x in np.asarray(row).reshape(-1)]
+    dis = row[1]
+    name = lambda r: f"{'B' if (dis >> r) & 1 else ''}{r}"
+    out = [f"success={row[0]} dishonest={_bits(dis)} empty V={_bits(row[2])} status={row[3]}"]
+    if not isinstance(events, list):
+        events = trace_events([counts], [events])
+    for r in range(1, n + 1):
+        for head, pkt in events[r]:
+            f = event_fields(head)
+            if f["kind"] == EV_RECV:
+                what = f"accepted {_packet_text(pkt, f['len'])}" if f["code"] == 0 else \
+                    f"rejected, {VERDICTS[f['code']]}" if f["code"] <= 3 else \
+                    f"consistent, not taken ({VERDICTS[f['code']]}: {_packet_text(pkt, f['len'])})"
+                out.append(f"[{name(r)} <- {name(f['peer'])}] round {f['round']}: {what}")
+            elif f["kind"] == EV_SEND:
+                act = "" if f["code"] == EV_HONEST else f" (action: {ACTIONS[f['code']]})"
+                what = "does not send" if f["slot"] == EV_SLOT_MUTED else \
+                    f"{'drops (mailbox full)' if f['slot'] == EV_SLOT_FULL else 'sends'} {_packet_text(pkt, f['len'])}"
+                out.append(f"[{name(r)} -> {f['peer']}] round {f['round']}: {what}{act}")
+            else:
+                dec = pkt - (1 << 32) if pkt >> 31 else pkt
+                v = "{" + ", ".join(str(b) for b in _bits(row[5 + 5 * r])) + "}"
+                out.append(f"[{name(r)}] decides {dec}" + (f", V = {v}" if r > 1 else " (the commander's order)"))
+        more = int(np.asarray(counts).reshape(-1)[r]) - len(events[r])
+        if more > 0:
+            out.append(f"[{name(r)}] ... {more} more event{'' if more == 1 else 's'} counted, not stored")
+    return "\n".join(out)

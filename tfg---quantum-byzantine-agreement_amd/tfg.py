@@ -49,6 +49,7 @@ def _sizes(text: str):
 
 
 SWEEP_MAX = 16  # scenarios of one --sweep run (QBA_MC_SWEEP_MAX)
+EXPLAIN_CAP = 1024  # events kept per rank of an --explain transcript (the rest are counted)
 
 
 def _scenarios(text: str, n_dishonest: int, montecarlo) -> list:
@@ -92,6 +93,10 @@ def _args(argv):
     ap.add_argument("--failures", type=int, default=0, metavar="K",
                     help="with --runs: after each summary line, the indices of up to K runs without success, to "
                          "replay under key seed + index; implies --tally")
+    ap.add_argument("--explain", type=int, default=0, metavar="K",
+                    help="with --runs: --failures K, and after each line's failed indices the transcript of those "
+                         "runs' protocol rounds as the device re-ran them (montecarlo.format_trace: every packet "
+                         "received with its verdict, every send with the traitor's action, every decision)")
     ap.add_argument("--flip", type=int, default=None, metavar="K",
                     help="with --runs: every measured qubit flips with probability K / 65536, 0 <= K <= 65535 "
                          "(montecarlo.noise_masks); implies --fused unless --tables is given; with K > 0 the "
@@ -123,6 +128,12 @@ def _args(argv):
             ap.error(f"--curve: at most {CURVE_MAX} checkpoints (the positional sizeL included), not {len(a.curve)}")
         if a.curve[0] < 0 or a.curve[-1] >= 1 << 31:
             ap.error("--curve: every sizeL must be in [0, 2^31)")
+    if a.explain < 0:
+        ap.error("--explain: K >= 0")
+    if a.explain:
+        if a.runs is None:
+            ap.error("--explain needs --runs")
+        a.failures = a.explain
     if a.failures < 0:
         ap.error("--failures: K >= 0")
     if (a.tally or a.failures) and a.runs is None:
@@ -279,6 +290,8 @@ def _montecarlo(a, eng, size_l) -> int:
     seed = secrets.randbits(62) if a.seed is None else a.seed
     t0 = time.perf_counter()
     how = {"tally": True, "failures": a.failures} if a.tally or a.failures else {}
+    if a.explain:
+        how["explain"] = EXPLAIN_CAP
     if a.flip:
         how["flip_q16"] = a.flip
     noise = f" flip={a.flip}/65536" if a.flip else ""
@@ -302,6 +315,10 @@ def _montecarlo(a, eng, size_l) -> int:
         if a.failures:
             print(f"Failed runs ({len(s['failed_runs'])} of {s['failed_total']}, key = seed + index, seed={seed}): "
                   + " ".join(str(i) for i in s["failed_runs"]))
+        if a.explain:
+            for i, row, counts, events in zip(s["failed_runs"], *s["trace"]):
+                print(f"Run {i}:")
+                print(montecarlo.format_trace(a.parties, row, counts, events))
     if a.timing:
         print(f"wall {time.perf_counter() - t0:.3f} s ({a.runs} instances on the device)")
     return 0

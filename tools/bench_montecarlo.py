@@ -53,6 +53,13 @@ instances x n = 7 x sizeL = 1e5, 2 dishonest, on one GPU.
       the same grid, the S timed as one interval; the rows of the two are
       compared at the timed shape.  One JSON line per --sweep and shape.
 
+  --trace  another mode, per --sizeL: the montecarlo_trace_sampled call at 16
+      and at --instances indices (cap 256, the reference policy word) beside
+      montecarlo_sampled(..., adversary=0xF) of the same number of instances --
+      the yardstick: the trace is that call plus the event stores -- with the
+      rows of the two compared, and the host wall time of montecarlo.trace_host
+      for 16 runs on the engine's own count tables.
+
 (a), (b), (d), the --tally calls, the --flip calls and the --curve pair are device-event times of single calls on warm code: median, min
 and max over --repeats launches after --warmup launches.  (c) is host wall
 time around runs that end in device synchronisation (each reads its tables
@@ -115,7 +122,13 @@ def main(argv=None) -> int:
     ap.add_argument("--sweep", action="append", default=None, metavar="K:POLICY,...",
                     help="time one sweep call over these scenarios against the separate curve calls with a policy, "
                          "at each --sizeL (one checkpoint) or each --curve; repeatable; nothing else is measured")
+    ap.add_argument("--trace", action="store_true",
+                    help="time montecarlo_trace_sampled at 16 and at --instances indices beside montecarlo_sampled "
+                         "with the reference policy word at the same shapes, and the host wall time of trace_host "
+                         "for 16 runs, at each --sizeL; nothing else is measured")
     a = ap.parse_args(argv)
+    if a.trace and (a.sweep or a.adversary or a.flip or a.curve or a.tally or a.tables):
+        ap.error("--trace goes with --sizeL alone")
     if a.sweep and (a.flip or a.tally or a.tables or a.adversary):
         ap.error("--sweep goes with --sizeL or --curve alone")
     if a.adversary and (a.flip or a.curve or a.tally or a.tables):
@@ -124,7 +137,9 @@ def main(argv=None) -> int:
         ap.error("--tables needs --flip and goes with neither --curve nor --tally")
 
     eng = importlib.import_module(f"{PKG}.engine").Engine(0)
-    if a.sweep:
+    if a.trace:
+        lines = [json.dumps(_measure_trace(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
+    elif a.sweep:
         shapes = [[s] for s in (a.sizeL or [])] + [sorted({int(c) for c in text.split(",")}) for text in a.curve or []]
         lines = [json.dumps(_measure_sweep(a, eng, counts, text)) for text in a.sweep for counts in shapes or [[100_000]]]
     elif a.adversary:
@@ -291,6 +306,36 @@ def _measure_adversary(a, eng, size_l) -> dict:
     # a verdict only for 0xF (equal rows), and only where the min-max ranges do not overlap
     res["reference_word_slower"] = r["min_ms"] > hi
     res["reference_word_faster"] = r["max_ms"] < lo
+    return res
+
+
+def _measure_trace(a, eng, size_l) -> dict:
+    """--trace: the trace call at 16 and at --instances indices beside the
+    decision call under the reference word at the same shapes (the yardstick:
+    the trace is that call plus the event stores), and trace_host for 16 runs."""
+    import torch
+    mc = importlib.import_module(f"{PKG}.montecarlo")
+    n, nd, cap = a.parties, a.dishonest, 256
+    res = {"config": {"n": n, "sizeL": size_l, "dishonest": nd, "seed": a.seed, "cap": cap, "adversary": "0xf",
+                      "device": torch.cuda.get_device_name(0)}, "indices": {}}
+    for k in sorted({16, a.instances}):
+        idx = torch.arange(k, dtype=torch.int64, device=eng.device)
+        out = eng.montecarlo_trace_sampled(n, nd, a.seed, idx, size_l, cap=cap)
+        rows = eng.montecarlo_sampled(n, nd, a.seed, k, size_l, adversary=0xF)
+        t = {"trace": _events(lambda: eng.montecarlo_trace_sampled(n, nd, a.seed, idx, size_l, cap=cap, out=out),
+                              a.warmup, a.repeats),
+             "decide": _events(lambda: eng.montecarlo_sampled(n, nd, a.seed, k, size_l, rows, adversary=0xF),
+                               a.warmup, a.repeats)}
+        t["rows_equal"] = bool(torch.equal(out[0], rows))
+        t["events_per_instance"] = float(out[1].sum().item()) / k
+        t["events_past_cap"] = int((out[1] > cap).sum().item())
+        t["trace_over_decide_at_median"] = t["trace"]["median_ms"] / t["decide"]["median_ms"]
+        res["indices"][str(k)] = t
+    t0 = time.perf_counter()  # the host specification on the engine's own count tables
+    host = mc.trace_host(n, size_l, nd, range(16), a.seed, eng)
+    res["trace_host_16_runs_wall_s"] = time.perf_counter() - t0
+    dev = eng.montecarlo_trace_sampled(n, nd, a.seed, list(range(16)), size_l, cap=cap)
+    res["trace_host_rows_equal_device"] = bool((dev[0].cpu().numpy() == host[0]).all())
     return res
 
 
