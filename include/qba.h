@@ -703,6 +703,39 @@ QBA_API int qba_philox_dev(qba_ctx *ctx, const uint32_t *ctr_dev, int64_t n, uin
  * reduction first.  Results are bit-identical under every setting. */
 QBA_API int qba_test_set_knobs(qba_ctx *ctx, uint64_t chunk_entries, int64_t pb_min_entries, int list_grid);
 
+/* ---- colluding traitors -------------------------------- */
+/* The two _adv curve calls with a second 32-bit word, `coal`, last: the
+ * dishonest lieutenants withhold accepted packets from honest ones and inject
+ * them in a late round R, padded with the coalition's tuples to the length that
+ * round demands.
+ *   bit  0       on       1: the traitors collude
+ *   bits [4:6)   when     R: 0 n_dishonest + 1 (the last round), 1
+ *                         max(1, n_dishonest) (the last round whose acceptances
+ *                         are relayed)
+ *   bits [8:10)  targets  the honest lieutenants packets are withheld from and
+ *                         injected to: 0 all, 1 even ranks, 2 the lowest-ranked
+ *   bit  12      starve   a dishonest commander sends v1 to every honest and v2
+ *                         to every dishonest lieutenant
+ * coal == 0 is no coalition: the call writes the rows of the _adv curve call
+ * word for word.  Any other bit, when > 1, targets == 3 or a field set without
+ * `on` is QBA_EINVAL (the message names the field), checked right after `adv`
+ * and before ctx.  The out layout, every other check and its order, asynchrony
+ * and capture legality are those of the _adv curve calls; a single sizeL is a
+ * curve of one checkpoint; qba_montecarlo_tally takes the rows as they are.
+ * The sampled kernel holds a wavefront's hold lists in LDS beside what the
+ * curve kernels hold: qba_montecarlo_coal_shape reports its launch shape as
+ * qba_montecarlo_curve_shape does theirs.  Specification:
+ * montecarlo.CoalitionParty. */
+QBA_API int qba_montecarlo_curve_sampled_coal(qba_ctx *ctx, int n_parties, int n_dishonest, uint64_t seed_base,
+                                              int64_t n_instances, const uint32_t *counts_host, int n_counts,
+                                              uint32_t flip_q16, int32_t *out_dev, qba_stream stream, uint32_t adv,
+                                              uint32_t coal);
+QBA_API int qba_montecarlo_curve_lists_coal(qba_ctx *ctx, int n_parties, int n_dishonest, uint64_t seed_base,
+                                            int64_t n_instances, const uint32_t *counts_host, int n_counts,
+                                            const uint8_t *lists_dev, uint64_t ld, uint64_t inst_stride,
+                                            int32_t *out_dev, qba_stream stream, uint32_t adv, uint32_t coal);
+QBA_API int qba_montecarlo_coal_shape(int n_parties, int *waves, int64_t *lds_bytes, int *wgs_per_cu);
+
 #ifdef __cplusplus
 }
 #endif

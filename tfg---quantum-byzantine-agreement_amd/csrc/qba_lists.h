@@ -54,6 +54,7 @@ struct QbaMc {
                  // `noise` at run time: steps == 0 is no noise
   int use_adv;
   QbaMcScen scen;  // read by the sweep kernel alone (qba_montecarlo_sweep_sampled), which takes no n_dis / adv
+  uint32_t coal;   // the coalition word, read by the coalition kernel alone (qba_montecarlo_curve_sampled_coal)
 };
 
 template <int NP>
@@ -77,6 +78,12 @@ int qba_launch_mc_adv(qba_ctx *ctx, const QbaMc &M);
 // the curve under every scenario of M.scen, through the sweep kernel (qba_mc_sweep_inst.hip)
 template <int NP>
 int qba_launch_mc_sweep(qba_ctx *ctx, const QbaMc &M);
+// the curve under a policy and a coalition word, through the coalition kernel (qba_mc_coal_inst.hip)
+template <int NP>
+int qba_launch_mc_coal(qba_ctx *ctx, const QbaMc &M);
+// qba_montecarlo_coal_shape (qba_mc_coal_inst.hip)
+template <int NP>
+void qba_mc_coal_shape_n(int *waves, int64_t *lds, int *wgs);
 // qba_montecarlo_shape, or (curve) qba_montecarlo_curve_shape
 template <int NP>
 void qba_mc_shape_n(int curve, int *waves, int64_t *lds, int *wgs);

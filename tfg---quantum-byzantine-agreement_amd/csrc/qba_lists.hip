@@ -4,6 +4,7 @@
 
 #include "qba_lists.h"
 #include "qba_proto_adv.h"
+#include "qba_proto_coal.h"
 
 // Experiment builds only (tools/exp): restrict instantiation to one n.
 #ifndef QBA_ONLY_N
@@ -193,6 +194,26 @@ extern "C" int qba_montecarlo_curve_sampled_adv(qba_ctx *ctx, int n, int n_dis, 
                   out, stream, &adv);
 }
 
+// The curve call with colluding traitors: the _adv
+// curve call's arguments, then the coalition word, checked right after the
+// policy word and before ctx.
+extern "C" int qba_montecarlo_curve_sampled_coal(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
+                                                 const uint32_t *counts, int n_counts, uint32_t flip_q16,
+                                                 int32_t *out, qba_stream stream, uint32_t adv, uint32_t coal) {
+  const char *who = "qba_montecarlo_curve_sampled_coal";
+  QbaMc M{who, nullptr, seed_base, n_inst, n_dis, out, (hipStream_t)stream, {}, 1, {}, adv, 1, {}, coal};
+  const char *bad = bad_flip(flip_q16);
+  if (!bad) bad = qba_adv_bad(adv);
+  if (!bad) bad = qba_coal_bad(coal);
+  if (int rc = qba_mc_curve_check(who, ctx, n, n_dis, n_inst, counts, n_counts, out, &M.counts, bad)) return rc;
+  if (flip_q16) M.noise = qba_noise_of(flip_q16);
+  if (int rc = need_program(ctx, n, who)) return rc;
+  if (n_inst == 0) return QBA_OK;
+  if (int rc = qba_set_device(ctx)) return rc;
+  M.ps = (const QbaProgramSet *)ctx->prog_dev[n];
+  return with_n(n, [&](auto k) { return qba_launch_mc_coal<decltype(k)::value>(ctx, M); });
+}
+
 // The curve call under every scenario of a list: one
 // pass over the entries, the rounds once per checkpoint and scenario.  Checked
 // in the order counts, flip_q16, scenarios, ctx (qba_mc_sweep_check).
@@ -244,6 +265,16 @@ extern "C" int qba_montecarlo_curve_shape(int n, int *waves, int64_t *lds_bytes,
 
 extern "C" int qba_montecarlo_shape(int n, int *waves, int64_t *lds_bytes, int *wgs_per_cu) {
   return mc_shape("qba_montecarlo_shape", n, 0, waves, lds_bytes, wgs_per_cu);
+}
+
+// The shape of the coalition kernel (its waves hold their hold lists too)
+extern "C" int qba_montecarlo_coal_shape(int n, int *waves, int64_t *lds_bytes, int *wgs_per_cu) {
+  if (n < 1 || n > QBA_MAX_PARTIES || !waves || !lds_bytes || !wgs_per_cu)
+    return qba_fail(QBA_EINVAL, "qba_montecarlo_coal_shape: n_parties must be in [1, 15] and the outputs not NULL");
+  return with_n(n, [&](auto k) {
+    qba_mc_coal_shape_n<decltype(k)::value>(waves, lds_bytes, wgs_per_cu);
+    return (int)QBA_OK;
+  });
 }
 
 extern "C" int qba_montecarlo_program_shape(qba_ctx *ctx, int n, int curve, int *sampler, int *waves_compiled,

@@ -17,6 +17,7 @@
 //   qba_k_mc_lists: lane l distils entries l, l + 64, ... of the instance's
 //             rows into the same masks (mc_entry, qba_proto_rounds.h)
 #include "qba_proto_adv.h"  // the entry points' policy check and launches; the kernels here keep qba_proto_rounds.h
+#include "qba_proto_coal.h"  // ... and the coalition word's check and launch
 
 namespace {
 
@@ -334,6 +335,27 @@ extern "C" int qba_montecarlo_curve_lists_adv(qba_ctx *ctx, int n, int n_dis, ui
   return launch_chunks(ctx, n_inst, [&](int64_t first, dim3 grid) {
     qba_launch_mc_curve_lists_adv(grid, lds, (hipStream_t)stream, n, n_dis, seed_base, first, n_inst, lists, ld,
                                   inst_stride, out, cv, adv);
+  });
+}
+
+// qba_montecarlo_curve_lists_adv with colluding traitors (DESIGN.md section
+// 13.10): the kernel of qba_proto_coal.hip, whose hold lists sit behind the
+// accumulator area.  The coalition word is checked right after the policy word.
+extern "C" int qba_montecarlo_curve_lists_coal(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
+                                               const uint32_t *counts, int n_counts, const uint8_t *lists,
+                                               uint64_t ld, uint64_t inst_stride, int32_t *out, qba_stream stream,
+                                               uint32_t adv, uint32_t coal) {
+  const char *who = "qba_montecarlo_curve_lists_coal";
+  QbaMcCounts cv;
+  const char *bad = qba_adv_bad(adv);
+  int rc = qba_mc_curve_check(who, ctx, n, n_dis, n_inst, counts, n_counts, out, &cv, bad ? bad : qba_coal_bad(coal));
+  if (rc || (rc = lists_check(who, n, n_inst, cv.c[cv.n - 1], lists, ld, inst_stride)) || n_inst == 0) return rc;
+  const int G = n + 1, w = 1 << qba_nq(n);
+  const size_t lds = (size_t)(PROTO_S_WORDS + ((proto_box_words(G, w) + 3) & ~3) + ((mc_acc_words(G, w) + 3) & ~3) +
+                              proto_hold_words(G, w)) * sizeof(uint32_t);  // <= 38064 B
+  return launch_chunks(ctx, n_inst, [&](int64_t first, dim3 grid) {
+    qba_launch_mc_coal_lists(grid, lds, (hipStream_t)stream, n, n_dis, seed_base, first, n_inst, lists, ld,
+                             inst_stride, out, cv, adv, coal);
   });
 }
 

@@ -490,6 +490,47 @@ class Engine:
              (C.c_uint32 * len(cs))(*cs), len(cs), _ptr(lists), ld, stride, _ptr(out), self.stream())
         return out
 
+    # -- the curve with colluding traitors (qba_montecarlo_curve_*_coal) -----------
+    @staticmethod
+    def _check_coalition(coalition) -> int:
+        """A coalition word (None: 0, no coalition) checked on the host."""
+        from .montecarlo import check_coalition
+        return 0 if coalition is None else check_coalition(coalition)
+
+    def montecarlo_curve_sampled_coal(self, n: int, n_dishonest: int, seed_base: int, n_inst: int, counts,
+                                      out: Optional[torch.Tensor] = None, flip_q16: int = 0,
+                                      adversary: Optional[int] = None, coalition: Optional[int] = None) -> torch.Tensor:
+        """montecarlo_curve_sampled with colluding traitors
+        (qba_montecarlo_curve_sampled_coal): the same rows layout, the
+        dishonest parties under the policy ``adversary`` (None: the reference's
+        0xF) and the coalition word ``coalition`` (montecarlo.coalition; None
+        or 0: no coalition, the rows of the ``adversary`` call)."""
+        self._check_n(n)
+        cs = self._check_curve(n, n_dishonest, n_inst, counts)
+        flip = self._check_flip(flip_q16)
+        adv = self._check_adversary(0xF if adversary is None else adversary)
+        coal = self._check_coalition(coalition)
+        self.prepare(n)
+        out = self._rows_out(n, n_inst, out, len(cs))
+        call("qba_montecarlo_curve_sampled_coal", self.ctx, n, n_dishonest, _u64(seed_base), n_inst,
+             (C.c_uint32 * len(cs))(*cs), len(cs), flip, _ptr(out), self.stream(), adv, coal)
+        return out
+
+    def montecarlo_curve_lists_coal(self, n: int, n_dishonest: int, seed_base: int, lists, counts,
+                                    out: Optional[torch.Tensor] = None, adversary: Optional[int] = None,
+                                    coalition: Optional[int] = None) -> torch.Tensor:
+        """The same from injected lists (qba_montecarlo_curve_lists_coal), as
+        montecarlo_curve_lists takes them."""
+        self._check_n(n)
+        cs = self._check_curve(n, n_dishonest, 0, counts)
+        adv = self._check_adversary(0xF if adversary is None else adversary)
+        coal = self._check_coalition(coalition)
+        lists, n_inst, ld, stride = self._mc_lists(n, lists, cs[-1])
+        out = self._rows_out(n, n_inst, out, len(cs))
+        call("qba_montecarlo_curve_lists_coal", self.ctx, n, n_dishonest, _u64(seed_base), n_inst,
+             (C.c_uint32 * len(cs))(*cs), len(cs), _ptr(lists), ld, stride, _ptr(out), self.stream(), adv, coal)
+        return out
+
     # -- a grid of scenarios per checkpoint in one pass (qba_montecarlo_sweep_*) ----
     SWEEP_MAX = 16  # QBA_MC_SWEEP_MAX
 

@@ -54,6 +54,13 @@ A sweep (:func:`sweep`, ``Engine.montecarlo_sweep_sampled`` /
 curve under a whole grid of scenarios ``(n_dishonest, word)`` in the same one
 pass: the lists do not depend on either.  :func:`sweep_host` is its
 specification.
+
+Colluding traitors (``coalition=word`` on :func:`run`, :func:`curve` and their
+host forms): a second word, built by
+:func:`coalition` (presets in :data:`COALITIONS`), under which the dishonest
+lieutenants withhold accepted packets from the honest ones and inject them in a
+late round, padded with each other's tuples.  :class:`CoalitionParty` is the
+definition; ``None`` and ``0`` are "no coalition".
 """
 from __future__ import annotations
 
@@ -356,9 +363,251 @@ def adversary_party(word: int, base=None):
     return type(f"AdversaryParty_{word:x}", bases, {"adv": word})
 
 
+# ---------------------------------------------------------------------------
+# Colluding traitors
+# ---------------------------------------------------------------------------
+WHEN_LAST, WHEN_RELAYED = 0, 1
+TARGETS_ALL, TARGETS_EVEN, TARGETS_LOWEST = 0, 1, 2
+_COAL_VALID = 0x1331
+
+
+def check_coalition(word) -> int:
+    """``word`` as an int when it is a valid coalition word (0: no coalition);
+    QbaError otherwise (a reserved bit, when > 1, targets > 2, or a field set
+    without ``on``)."""
+    try:
+        c = int(word)
+    except (TypeError, ValueError):
+        raise QbaError(f"coalition must be an integer word, not {word!r}") from None
+    if c < 0 or c & ~_COAL_VALID:
+        raise QbaError(f"coalition word {c:#x} sets a reserved bit")
+    if (c >> 4) & 3 > 1:
+        raise QbaError(f"coalition word {c:#x}: the when field must be <= 1")
+    if (c >> 8) & 3 > 2:
+        raise QbaError(f"coalition word {c:#x}: the targets field must be <= 2")
+    if not c & 1:
+        for name, field in (("when", (c >> 4) & 3), ("targets", (c >> 8) & 3), ("starve", (c >> 12) & 1)):
+            if field:
+                raise QbaError(f"coalition word {c:#x} sets the {name} field without on")
+    return c
+
+
+def coalition(when: int = WHEN_LAST, targets: int = TARGETS_ALL, starve: bool = False) -> int:
+    """The word of a coalition of all dishonest parties (bit 0, ``on``, set).
+
+    ``when``     the round R in which the receivers process the held packets:
+                 0 ``n_dishonest + 1`` (the last round: an acceptance there is
+                 never relayed), 1 ``max(1, n_dishonest)`` (the last round whose
+                 acceptances are still relayed).
+    ``targets``  the honest lieutenants that packets are withheld from and
+                 injected to: 0 all, 1 those of even rank, 2 the lowest-ranked.
+    ``starve``   a dishonest commander sends v1 to every honest lieutenant and
+                 v2 to every dishonest one."""
+    if when not in (0, 1):
+        raise QbaError("when is 0 (the last round) or 1 (the last relayed round)")
+    if targets not in (0, 1, 2):
+        raise QbaError("targets is 0 (all honest lieutenants), 1 (even ranks) or 2 (the lowest-ranked)")
+    return check_coalition(1 | int(when) << 4 | int(targets) << 8 | (1 << 12 if starve else 0))
+
+
+COALITIONS = {
+    "late": coalition(),
+    "late_relayed": coalition(when=WHEN_RELAYED),
+    "late_one": coalition(targets=TARGETS_LOWEST),
+    "starve_late": coalition(targets=TARGETS_EVEN, starve=True),
+}
+
+
+def parse_coalition(text) -> int:
+    """A preset name of :data:`COALITIONS` or a number (``0x...`` or decimal)
+    as a checked coalition word."""
+    if isinstance(text, str):
+        if text in COALITIONS:
+            return COALITIONS[text]
+        try:
+            text = int(text, 0)
+        except ValueError:
+            raise QbaError(f"coalition {text!r} is neither a number nor one of {sorted(COALITIONS)}") from None
+    return check_coalition(text)
+
+
+class CoalitionRun:
+    """What the traitors of one run share: ``parties`` {rank: party}, filled as
+    the parties are made.  The dishonest set is rank 0's draw; a lieutenant
+    reads it only after the tables of rank 0 have reached it, which rank 0
+    sends after the draw.  The traitors' descriptors under a P_u come from the
+    count tables, which every rank holds."""
+
+    def __init__(self):
+        self.parties: Dict[int, protocol.Party] = {}
+
+    def dishonest(self) -> frozenset:
+        return frozenset(int(r) for r in self.parties[0].dishonest_ids)
+
+
+class CoalitionParty(AdversaryParty):
+    """AdversaryParty whose dishonest parties collude as the coalition word
+    ``coal`` says (class attributes: :func:`coalition_party` makes the subclass
+    of a pair of words; ``run_shared`` is the :class:`CoalitionRun` that
+    :func:`run_host` hands over per instance, and without one -- the class
+    used outside :func:`run_host` -- nobody colludes).  The specification of
+    the ``_coal`` kernels; with ``coal == 0`` it is AdversaryParty.
+
+    A dishonest lieutenant under ``on`` that accepts a packet in round r (0:
+    the commander's epoch) serves its destinations in ascending order: a
+    dishonest one gets the packet as it was handed over, with no draw; a target
+    gets nothing while r < R - 1, and the handed packet goes once to the hold
+    list; every other one is served as AdversaryParty serves it (a mutation
+    that stays, stays for these destinations only).  In round R - 1, after its
+    inbox, it sends the hold list in order to every target in ascending rank,
+    each packet with a P and no empty tuple padded to R tuples from the pool:
+    the dishonest lieutenants' tuples in ascending rank, then under a
+    dishonest commander its tuple (row 0) and, when v != u, its extra list's
+    (row 1, Lc: equal to u on all of P_u, so Cond2 lets it pass under another
+    v only)."""
+
+    coal = 0
+    run_shared: Optional[CoalitionRun] = None
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self._acc_rnd = 0      # the round of the packet being processed (0: the commander's epoch)
+        self._seen_rounds = 0  # rounds whose inbox has been drained
+        self._left = 0         # packets of the current round not yet processed
+        self.hold = []
+        if self.run_shared is not None:
+            self.run_shared.parties[self.rank] = self
+
+    # -- the word ------------------------------------------------------------
+    @property
+    def colluding(self) -> bool:
+        return bool(self.coal & 1) and self.dishonest and self.run_shared is not None
+
+    def delivery_round(self) -> int:
+        return self.n_dis + 1 if (self.coal >> 4) & 3 == 0 else max(1, self.n_dis)
+
+    def targets(self) -> list:
+        if self.run_shared is None:
+            return []
+        dis = self.run_shared.dishonest()
+        honest = [r for r in range(2, self.n + 1) if r not in dis]
+        sel = (self.coal >> 8) & 3
+        return honest if sel == 0 else [r for r in honest if r % 2 == 0] if sel == 1 else honest[:1]
+
+    # -- the commander -------------------------------------------------------
+    def comm_broadcast(self):
+        if self.rank != 1 or not self.colluding or not (self.coal >> 12) & 1:
+            return super().comm_broadcast()
+        dis = self.run_shared.dishonest()
+        v1 = self.rng.randint(self.w)
+        v2 = self.rng.randint(self.w)
+        while v2 == v1:
+            v2 = self.rng.randint(self.w)
+        for dest in range(2, self.n + 1):
+            v = v2 if dest in dis else v1
+            self.send(dest, self.p_for(v), v, set())
+
+    # -- a lieutenant --------------------------------------------------------
+    def lieu_receive(self, P, v, L, rnd, pre=None):
+        self._acc_rnd = rnd
+        super().lieu_receive(P, v, L, rnd, pre)
+        self._left -= 1
+        if self._left == 0 and self.colluding and rnd == self.delivery_round() - 1:
+            self.deliver()
+
+    def precheck(self, inbox):
+        """Called once per round with the drained inbox: the point from which
+        the end of the round's inbox walk is counted."""
+        self._seen_rounds += 1
+        self._left = len(inbox)
+        if not inbox and self.colluding and self._seen_rounds == self.delivery_round() - 1:
+            self.deliver()
+        return super().precheck(inbox)
+
+    def lieu_broadcast(self, P, v, L):
+        if not self.colluding:
+            return super().lieu_broadcast(P, v, L)
+        acts = [a for a in range(5) if (self.adv >> a) & 1]
+        order, fresh = (self.adv >> 8) & 3, (self.adv >> 12) & 1
+        dis, targets = self.run_shared.dishonest(), self.targets()
+        early = self._acc_rnd < self.delivery_round() - 1
+        P0, v0, L0 = copy.copy(P), v, set(L)  # the packet as handed over; P and L below are working copies
+        P, L = copy.copy(P0), set(L0)
+        held = False
+        for dest in range(2, self.n + 1):
+            if dest == self.rank:
+                continue
+            if dest in dis:
+                self.send(dest, P0, v0, L0)
+                continue
+            if early and dest in targets:
+                if not held:
+                    self.hold.append((copy.copy(P0), v0, set(L0)))
+                    held = True
+                continue
+            go = 1
+            if fresh:
+                P, v, L = copy.copy(P0), v0, set(L0)
+            action = acts[self.rng.randint(len(acts))]
+            if action == ACT_MUTE:
+                go = self.rng.randint(2)
+            elif action == ACT_REORDER:
+                if order == ORDER_LOW:
+                    v = 1 if int(v) == 0 else 0
+                else:
+                    v = self.rng.randint(self.n + 1 if order == ORDER_REFERENCE else self.w)
+            elif action == ACT_CLEAR_P:
+                P.clear()
+            elif action == ACT_CLEAR_L:
+                L.clear()
+            if go:
+                self.send(dest, P, v, L)
+
+    def pool(self, u: int, v: int) -> list:
+        """The coalition's tuples under P_u, in the order they are offered."""
+        dis = self.run_shared.dishonest()
+        rows = [g for g in range(2, self.n + 1) if g in dis]
+        if 1 in dis:  # row 0 is the commander's list, row 1 its extra list Lc: u on all of P_u
+            rows.append(0)
+            if int(v) != u:
+                rows.append(1)
+        return [(g, self.tables.desc(g, u)) for g in rows]
+
+    def pad(self, P, v, L) -> None:
+        """A held packet with a P and no empty tuple takes pool tuples it does
+        not hold yet until it has R of them or the pool is exhausted."""
+        if P.u is None or () in L:
+            return
+        R = self.delivery_round()
+        for _, d in self.pool(P.u, v):
+            if len(L) >= R:
+                break
+            L.add(d)  # a tuple that is there already (a duplicated row's, the sender's own) adds nothing
+
+    def deliver(self):
+        targets = self.targets()
+        for P, v, L in self.hold:
+            self.pad(P, v, L)
+            for dest in targets:
+                self.send(dest, P, v, L)
+        self.hold = []
+
+
+def coalition_party(adv: int, coal: int, base=None):
+    """The :class:`CoalitionParty` subclass of a policy word and a coalition
+    word, for the ``party_cls`` seam of :func:`run_host` (which sets
+    ``run_shared`` per instance); ``base`` as in :func:`adversary_party`."""
+    adv, coal = check_adversary(adv), check_coalition(coal)
+    if base is not None and issubclass(base, CoalitionParty):  # an observing subclass: the words are set on it
+        bases = (base,)
+    else:
+        bases = (CoalitionParty,) if base in (None, CountParty, AdversaryParty) else (CoalitionParty, base)
+    return type(f"CoalitionParty_{adv:x}_{coal:x}", bases, {"adv": adv, "coal": coal})
+
+
 def run_host(n: int, sizeL: int, n_dishonest: int, n_inst: int, seed_base: int, engine, lists=None,
              party_cls=None, rng_factory: Optional[Callable] = None, flip_q16: int = 0,
-             adversary: Optional[int] = None) -> np.ndarray:
+             adversary: Optional[int] = None, coalition: Optional[int] = None) -> np.ndarray:
     """The specification of qba_protocol_batched: CountParty under
     ``protocol.run_local`` (LocalWorld's barrier-epoch delivery: a round's inbox
     is everything sent in the previous epoch, in (source, sequence) order,
@@ -377,9 +626,17 @@ def run_host(n: int, sizeL: int, n_dishonest: int, n_inst: int, seed_base: int, 
     ``adversary=word``: the dishonest parties follow that policy
     (:func:`adversary_party` of ``party_cls``); ``None`` is the reference's
     rule, and ``0xF`` gives the same rows.
+
+    ``coalition=word``: the dishonest parties collude (:class:`CoalitionParty`
+    under ``adversary``, or the reference's rule); ``None`` and ``0`` are no
+    coalition and call what is called without the argument; ``party_cls`` may
+    then be an observing :class:`CoalitionParty` subclass.
     """
     flip = _check_flip(flip_q16)
-    if adversary is not None:
+    coal = 0 if coalition is None else check_coalition(coalition)
+    if coal:
+        party_cls = coalition_party(ADV_REFERENCE if adversary is None else adversary, coal, party_cls)
+    elif adversary is not None:
         party_cls = adversary_party(adversary, party_cls)
     out = np.zeros((n_inst, out_words(n)), np.int32)
     make = rng_factory or ProtocolRng
@@ -396,8 +653,11 @@ def run_host(n: int, sizeL: int, n_dishonest: int, n_inst: int, seed_base: int, 
         if flip and sizeL > 0:
             clean = engine.sample(n, key, 0, sizeL) if mine is None else np.asarray(mine)[:, :sizeL]
             mine = noisy_lists(n, key, _host_lists(clean, sizeL), flip)
+        cls = party_cls or CountParty
+        if coal:  # what the traitors of this instance share
+            cls = type(cls.__name__, (cls,), {"run_shared": CoalitionRun()})
         run = protocol.run_local(n, sizeL, n_dishonest, engine, lists=mine,
-                                 list_seed=key, party_cls=_recording(party_cls or CountParty, parties),
+                                 list_seed=key, party_cls=_recording(cls, parties),
                                  rng_factory=factory)
         status = ST_RNG if any(getattr(r, "capped", False) for r in rngs) else 0
         row = out[i]
@@ -636,7 +896,7 @@ def masks_from_lists(n: int, lists) -> dict:
 
 def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, packed: bool = True,
         batch: int = 4096, path: str = "tables", tally: bool = False, failures: int = 0, flip_q16: int = 0,
-        adversary: Optional[int] = None, explain: int = 0) -> dict:
+        adversary: Optional[int] = None, explain: int = 0, coalition: Optional[int] = None) -> dict:
     """``runs`` independent instances on the device, ``batch`` at a time, batch
     at offset ``off`` under key ``seed + off``; only the result rows are copied
     to the host.  Returns :func:`summarize` of all rows.
@@ -667,9 +927,20 @@ def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, pack
     transcripts ``(rows, counts, events)`` of ``failed_runs`` with at most
     ``cap`` stored events per rank (``Engine.montecarlo_trace_sampled``, fed
     from the capture buffer on the device; :func:`format_trace` renders one).
-    Every path's rows are equal, so the fused trace explains them all."""
+    Every path's rows are equal, so the fused trace explains them all.
+
+    ``coalition=word`` (``path="fused"`` only, without ``explain``): the
+    dishonest parties collude (:func:`coalition`); the decisions go through the
+    coalition kernel as a curve of the one checkpoint ``sizeL``.  ``None`` and
+    ``0`` call what is called without the argument."""
     if path not in ("tables", "fused", "tables_noisy"):
         raise ValueError("path is 'tables', 'fused' or 'tables_noisy'")
+    if coalition is not None and check_coalition(coalition):
+        if path != "fused" or explain:
+            raise ValueError("coalition needs path='fused' and no explain: the tables path and the trace "
+                             "kernels do not collude")
+        return curve(n, [sizeL], n_dishonest, runs, seed, engine, batch=batch, tally=tally, failures=failures,
+                     flip_q16=flip_q16, adversary=adversary, coalition=coalition)[int(sizeL)]
     noise = {"flip_q16": _check_flip(flip_q16)} if flip_q16 else {}
     if noise and path == "tables":
         raise ValueError("flip_q16 > 0 needs path='fused' or path='tables_noisy'")
@@ -691,17 +962,20 @@ def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, pack
 
 
 def curve_host(n: int, counts, n_dishonest: int, n_inst: int, seed_base: int, engine, lists=None,
-               flip_q16: int = 0, adversary: Optional[int] = None) -> np.ndarray:
+               flip_q16: int = 0, adversary: Optional[int] = None, coalition: Optional[int] = None) -> np.ndarray:
     """The specification of the curve calls: the stack of :func:`run_host` at
     each count of ``counts``, int32 [len(counts), n_inst, out_words(n)].
     Injected ``lists`` [n_inst, n+1, >= max(counts)] are truncated to
     ``[:, :, :c]`` for the count c.  ``flip_q16`` as in :func:`run_host` (the
-    flips of entry e are the same at every count), and ``adversary``."""
+    flips of entry e are the same at every count), ``adversary`` and
+    ``coalition``."""
     counts = [int(c) for c in counts]
     li = None if lists is None else np.asarray(lists)
     noise = {"flip_q16": flip_q16} if flip_q16 else {}
     if adversary is not None:
         noise["adversary"] = adversary
+    if coalition is not None:
+        noise["coalition"] = coalition
     rows = [run_host(n, c, n_dishonest, n_inst, seed_base, engine, lists=None if li is None else li[:, :, :c],
                      **noise)
             for c in counts]
@@ -709,22 +983,32 @@ def curve_host(n: int, counts, n_dishonest: int, n_inst: int, seed_base: int, en
 
 
 def curve(n: int, counts, n_dishonest: int, runs: int, seed: int, engine, batch: int = 4096, tally: bool = False,
-          failures: int = 0, flip_q16: int = 0, adversary: Optional[int] = None, explain: int = 0) -> dict:
+          failures: int = 0, flip_q16: int = 0, adversary: Optional[int] = None, explain: int = 0,
+          coalition: Optional[int] = None) -> dict:
     """The failure curve over sizeL: ``runs`` instances, ``batch`` at a time as
     :func:`run` keys them, each decided at every sizeL of the strictly
     increasing ``counts`` by one montecarlo_curve_sampled call per batch.
     Returns ``{sizeL: summarize(...)}`` in checkpoint order; the summary at
     sizeL = c is that of ``run(n, c, ..., path="fused")``.  ``tally`` and
     ``failures`` as in :func:`run`, per checkpoint; ``flip_q16``,
-    ``adversary`` and ``explain`` as there (one trace call per checkpoint)."""
+    ``adversary`` and ``explain`` as there (one trace call per checkpoint).
+    ``coalition=word`` (not with ``explain``): one
+    montecarlo_curve_sampled_coal call per batch instead; ``None`` and ``0``
+    call what is called without it."""
     counts = [int(c) for c in counts]
     noise = {"flip_q16": _check_flip(flip_q16)} if flip_q16 else {}
     if adversary is not None:
         noise["adversary"] = check_adversary(adversary)
+    coal = 0 if coalition is None else check_coalition(coalition)
+    if coal and explain:
+        raise ValueError("explain is not built for a coalition: the trace kernels do not collude")
     if tally or failures:
         engine._check_curve(n, n_dishonest, 0, counts)  # before any device buffer: an empty list has no slice
 
     def decide(key, b, **into):
+        if coal:
+            return engine.montecarlo_curve_sampled_coal(n, n_dishonest, key, b, counts, coalition=coal, **into,
+                                                        **noise)
         return engine.montecarlo_curve_sampled(n, n_dishonest, key, b, counts, **into, **noise)
     ex = ([(c, n_dishonest, adversary) for c in counts], flip_q16, explain) if explain else None
     return dict(zip(counts, _batches(n, len(counts), runs, batch, seed, engine, decide, tally, failures, ex)))

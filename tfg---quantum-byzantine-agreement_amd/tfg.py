@@ -109,6 +109,11 @@ def _args(argv):
                     help="with --runs: the dishonest parties follow this policy, a preset (reference, relay, "
                          "reorder_low, mute, strip) or a policy word (montecarlo.adversary); the summary lines "
                          "end in adversary=0xWORD")
+    ap.add_argument("--collude", default=None, metavar="NAME|0xHEX",
+                    help="with --runs: the dishonest parties collude, a preset (late, late_relayed, late_one, "
+                         "starve_late) or a coalition word (montecarlo.coalition): they withhold packets from honest "
+                         "lieutenants and inject them in a late round, padded with each other's tuples; implies "
+                         "--fused; the summary lines end in collude=0xWORD; not with --sweep, --explain or --tables")
     ap.add_argument("--sweep", default=None, metavar="K:POLICY,...",
                     help="with --runs: decide every instance under each of these scenarios in one pass per batch "
                          "(montecarlo.sweep; at most 16, and 32 lines with --curve): K traitors following POLICY "
@@ -157,6 +162,18 @@ def _args(argv):
             a.adversary = montecarlo.parse_adversary(a.adversary)
         except montecarlo.QbaError as e:
             ap.error(f"--adversary: {e}")
+    if a.collude is not None:
+        if a.runs is None:
+            ap.error("--collude needs --runs")
+        if a.sweep is not None or a.explain or a.tables:
+            ap.error("--collude: not with --sweep, --explain or --tables (the sweep, trace and tables paths "
+                     "are not built for a coalition)")
+        from . import montecarlo
+        try:
+            a.collude = montecarlo.parse_coalition(a.collude)
+        except montecarlo.QbaError as e:
+            ap.error(f"--collude: {e}")
+        a.fused = True
     if a.sweep is not None:
         if a.runs is None:
             ap.error("--sweep needs --runs")
@@ -298,6 +315,9 @@ def _montecarlo(a, eng, size_l) -> int:
     if a.adversary is not None:
         how["adversary"] = a.adversary
         noise += f" adversary={a.adversary:#x}"
+    if a.collude is not None:
+        how["coalition"] = a.collude
+        noise += f" collude={a.collude:#x}"
     if a.sweep is not None:
         grid = montecarlo.sweep(a.parties, a.curve if a.curve is not None else [size_l], a.sweep, a.runs, seed, eng,
                                 batch=a.batch, **how)

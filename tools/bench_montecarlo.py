@@ -53,6 +53,14 @@ instances x n = 7 x sizeL = 1e5, 2 dishonest, on one GPU.
       the same grid, the S timed as one interval; the rows of the two are
       compared at the timed shape.  One JSON line per --sweep and shape.
 
+  --collude NAME|0xHEX  (repeatable) another mode, per --sizeL: the coalition
+      call (qba_montecarlo_curve_sampled_coal, one checkpoint) at coal = 0 -- the
+      rows of the _adv curve call, which is checked -- and under each coalition
+      word given, beside that _adv curve call, which is timed first and again
+      last in the same session, under each of the policies reference and
+      reorder_low (or those of --adversary).  A coalition runs another protocol:
+      its times are reported without a verdict, its success counts beside them.
+
   --trace  another mode, per --sizeL: the montecarlo_trace_sampled call at 16
       and at --instances indices (cap 256, the reference policy word) beside
       montecarlo_sampled(..., adversary=0xF) of the same number of instances --
@@ -122,6 +130,10 @@ def main(argv=None) -> int:
     ap.add_argument("--sweep", action="append", default=None, metavar="K:POLICY,...",
                     help="time one sweep call over these scenarios against the separate curve calls with a policy, "
                          "at each --sizeL (one checkpoint) or each --curve; repeatable; nothing else is measured")
+    ap.add_argument("--collude", action="append", default=None, metavar="NAME|0xHEX",
+                    help="time the coalition call at coal = 0 and under each of these coalition words beside the "
+                         "_adv curve call of one checkpoint, at each --sizeL, under the policies of --adversary "
+                         "(default reference and reorder_low); nothing else is measured")
     ap.add_argument("--trace", action="store_true",
                     help="time montecarlo_trace_sampled at 16 and at --instances indices beside montecarlo_sampled "
                          "with the reference policy word at the same shapes, and the host wall time of trace_host "
@@ -129,6 +141,8 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
     if a.trace and (a.sweep or a.adversary or a.flip or a.curve or a.tally or a.tables):
         ap.error("--trace goes with --sizeL alone")
+    if a.collude and (a.trace or a.sweep or a.flip or a.curve or a.tally or a.tables):
+        ap.error("--collude goes with --sizeL and --adversary alone")
     if a.sweep and (a.flip or a.tally or a.tables or a.adversary):
         ap.error("--sweep goes with --sizeL or --curve alone")
     if a.adversary and (a.flip or a.curve or a.tally or a.tables):
@@ -137,7 +151,9 @@ def main(argv=None) -> int:
         ap.error("--tables needs --flip and goes with neither --curve nor --tally")
 
     eng = importlib.import_module(f"{PKG}.engine").Engine(0)
-    if a.trace:
+    if a.collude:
+        lines = [json.dumps(_measure_collude(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
+    elif a.trace:
         lines = [json.dumps(_measure_trace(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
     elif a.sweep:
         shapes = [[s] for s in (a.sizeL or [])] + [sorted({int(c) for c in text.split(",")}) for text in a.curve or []]
@@ -306,6 +322,45 @@ def _measure_adversary(a, eng, size_l) -> dict:
     # a verdict only for 0xF (equal rows), and only where the min-max ranges do not overlap
     res["reference_word_slower"] = r["min_ms"] > hi
     res["reference_word_faster"] = r["max_ms"] < lo
+    return res
+
+
+def _measure_collude(a, eng, size_l) -> dict:
+    """--collude: per policy, the _adv curve call of one checkpoint first and last, the coalition call at
+    coal = 0 (equal rows, checked) and under each coalition word between them."""
+    import torch
+    mc = importlib.import_module(f"{PKG}.montecarlo")
+    n, nd, inst = a.parties, a.dishonest, a.instances
+    res = {"config": {"n": n, "sizeL": size_l, "dishonest": nd, "instances": inst, "seed": a.seed,
+                      "device": torch.cuda.get_device_name(0)}, "policies": {}}
+    for policy in a.adversary or ["reference", "reorder_low"]:
+        adv = mc.parse_adversary(policy)
+        rows = eng.montecarlo_curve_sampled(n, nd, a.seed, inst, [size_l], adversary=adv)
+        ref = rows.clone()
+        parent = lambda: eng.montecarlo_curve_sampled(n, nd, a.seed, inst, [size_l], rows, adversary=adv)  # noqa: E731
+        r = {"word": f"{adv:#x}", "adv_curve_call": _events(parent, a.warmup, a.repeats), "coalitions": {}}
+        r["adv_curve_call"]["successes"] = int(ref[0, :, 0].sum())
+        for name in ["0"] + [c for c in a.collude if c != "0"]:
+            coal = mc.parse_coalition(name)
+            t = _events(lambda: eng.montecarlo_curve_sampled_coal(n, nd, a.seed, inst, [size_l], rows, adversary=adv,
+                                                                  coalition=coal), a.warmup, a.repeats)
+            t["word"] = f"{coal:#x}"
+            t["rows_equal_adv_curve_call"] = bool(torch.equal(rows, ref))
+            t["successes"] = int(rows[0, :, 0].sum())
+            r["coalitions"][name] = t
+        r["adv_curve_call_again"] = _events(parent, a.warmup, a.repeats)
+        first, last = r["adv_curve_call"], r["adv_curve_call_again"]
+        base = min(first["median_ms"], last["median_ms"])
+        r["adv_curve_call_spread_at_median"] = abs(first["median_ms"] - last["median_ms"]) / base
+        for t in r["coalitions"].values():
+            t["over_adv_curve_call_at_median"] = t["median_ms"] / base
+        z = r["coalitions"]["0"]
+        lo, hi = min(first["min_ms"], last["min_ms"]), max(first["max_ms"], last["max_ms"])
+        # a verdict only for coal = 0 (equal rows), and only where the min-max ranges do not overlap
+        r["no_coalition_ranges_overlap"] = not (z["min_ms"] > hi or z["max_ms"] < lo)
+        r["no_coalition_slower"] = z["min_ms"] > hi
+        r["no_coalition_faster"] = z["max_ms"] < lo
+        res["policies"][policy] = r
     return res
 
 
