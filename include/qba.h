@@ -736,6 +736,55 @@ QBA_API int qba_montecarlo_curve_lists_coal(qba_ctx *ctx, int n_parties, int n_d
                                             int32_t *out_dev, qba_stream stream, uint32_t adv, uint32_t coal);
 QBA_API int qba_montecarlo_coal_shape(int n_parties, int *waves, int64_t *lds_bytes, int *wgs_per_cu);
 
+/* ---- lossy links ---------------------------------------- */
+/* The two _adv curve calls with a second 32-bit word, `net`, last: packets are
+ * lost in flight.
+ *   bits [0:16)  drop_q16  a packet on a lossy link is lost with probability
+ *                          drop_q16 / 65536
+ *   bit  16      cmd       1: the commander's n - 1 sends of epoch 0 cross a
+ *                          lossy link too; 0: only lieutenant-to-lieutenant
+ *                          packets do
+ * net == 0 is the perfect network: the call writes the rows of the _adv curve
+ * call word for word.  Any other bit, or cmd with drop_q16 == 0, is QBA_EINVAL
+ * (the message names the field), checked right after `adv` and before ctx.
+ *
+ * Loss is a pure function of the packet, not a stream position: no existing
+ * draw moves.  A packet is identified by the instance key
+ * key = seed_base + i, the epoch e in which it is sent (0 for the commander's
+ * epoch, including the relays lieutenants make after step 3a; r for round r),
+ * src, dest, and seq = the number of packets src has already handed to the
+ * link towards dest in epoch e (sends suppressed by action 0 are not handed
+ * over and do not count).  It is lost iff
+ *   (word(seq & 3) of philox4x32-10(ctr = {e, src | dest << 8, seq >> 2, 0x4E455457},
+ *                                   key = {key_lo, key_hi}) & 0xFFFF) < drop_q16.
+ * Counter word 3, 0x4E455457, is disjoint from the sampler's (0 or 1), the
+ * protocol's (0x51424150) and the noise stream's (0x4E4F4953).  The test
+ * applies to what the sender actually hands over, after a traitor's mutation,
+ * whether the sender is honest or not.
+ *
+ * The sender cannot tell: the row's `sent` counts the packet and seq advances.
+ * The packet takes no mailbox slot (the w-slot bound per (dest, src, round),
+ * its bounds check and status bit 0 hold), and the receiver never sees it: no
+ * accept, no reject, no V_i change, no relay.  Under cmd a lieutenant whose
+ * commander packet is lost skips step 3a altogether and takes part in the
+ * rounds with an empty V_i.  An honest lieutenant that ends with an empty V_i
+ * decides -1 (row word 2, tally words 2 and 15), as before.
+ *
+ * The out layout, status bits, every other check and its order, asynchrony and
+ * capture legality are those of the _adv curve calls; the calls allocate and
+ * copy nothing; a single sizeL is a curve of one checkpoint;
+ * qba_montecarlo_tally takes the rows as they are.  The kernels hold no LDS
+ * beyond the _adv curve kernels': qba_montecarlo_curve_shape is their launch
+ * shape.  Specification: montecarlo.NetParty, montecarlo.net_lost. */
+QBA_API int qba_montecarlo_curve_sampled_net(qba_ctx *ctx, int n_parties, int n_dishonest, uint64_t seed_base,
+                                             int64_t n_instances, const uint32_t *counts_host, int n_counts,
+                                             uint32_t flip_q16, int32_t *out_dev, qba_stream stream, uint32_t adv,
+                                             uint32_t net);
+QBA_API int qba_montecarlo_curve_lists_net(qba_ctx *ctx, int n_parties, int n_dishonest, uint64_t seed_base,
+                                           int64_t n_instances, const uint32_t *counts_host, int n_counts,
+                                           const uint8_t *lists_dev, uint64_t ld, uint64_t inst_stride,
+                                           int32_t *out_dev, qba_stream stream, uint32_t adv, uint32_t net);
+
 #ifdef __cplusplus
 }
 #endif

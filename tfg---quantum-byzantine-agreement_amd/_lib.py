@@ -87,6 +87,10 @@ SIGNATURES = {
     "qba_montecarlo_curve_lists_coal": [_p, C.c_int, C.c_int, _u64, _i64, C.POINTER(C.c_uint32), C.c_int, _p, _u64,
                                         _u64, _p, _p, C.c_uint32, C.c_uint32],
     "qba_montecarlo_coal_shape": [C.c_int, C.POINTER(C.c_int), _pi64, C.POINTER(C.c_int)],
+    "qba_montecarlo_curve_sampled_net": [_p, C.c_int, C.c_int, _u64, _i64, C.POINTER(C.c_uint32), C.c_int,
+                                         C.c_uint32, _p, _p, C.c_uint32, C.c_uint32],
+    "qba_montecarlo_curve_lists_net": [_p, C.c_int, C.c_int, _u64, _i64, C.POINTER(C.c_uint32), C.c_int, _p, _u64,
+                                       _u64, _p, _p, C.c_uint32, C.c_uint32],
     "qba_montecarlo_sweep_sampled": [_p, C.c_int, _u64, _i64, C.POINTER(C.c_uint32), C.c_int, C.POINTER(Scenario),
                                      C.c_int, C.c_uint32, _p, _p],
     "qba_montecarlo_sweep_lists": [_p, C.c_int, _u64, _i64, C.POINTER(C.c_uint32), C.c_int, C.POINTER(Scenario),

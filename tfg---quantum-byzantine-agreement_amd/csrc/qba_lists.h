@@ -55,6 +55,7 @@ struct QbaMc {
   int use_adv;
   QbaMcScen scen;  // read by the sweep kernel alone (qba_montecarlo_sweep_sampled), which takes no n_dis / adv
   uint32_t coal;   // the coalition word, read by the coalition kernel alone (qba_montecarlo_curve_sampled_coal)
+  uint32_t net;    // the network word, read by the lossy-network kernel alone (qba_montecarlo_curve_sampled_net)
 };
 
 template <int NP>
@@ -84,6 +85,9 @@ int qba_launch_mc_coal(qba_ctx *ctx, const QbaMc &M);
 // qba_montecarlo_coal_shape (qba_mc_coal_inst.hip)
 template <int NP>
 void qba_mc_coal_shape_n(int *waves, int64_t *lds, int *wgs);
+// the curve under a policy and a network word, through the lossy-network kernel (qba_mc_net_inst.hip)
+template <int NP>
+int qba_launch_mc_net(qba_ctx *ctx, const QbaMc &M);
 // qba_montecarlo_shape, or (curve) qba_montecarlo_curve_shape
 template <int NP>
 void qba_mc_shape_n(int curve, int *waves, int64_t *lds, int *wgs);

@@ -5,6 +5,7 @@
 #include "qba_lists.h"
 #include "qba_proto_adv.h"
 #include "qba_proto_coal.h"
+#include "qba_proto_net.h"
 
 // Experiment builds only (tools/exp): restrict instantiation to one n.
 #ifndef QBA_ONLY_N
@@ -212,6 +213,26 @@ extern "C" int qba_montecarlo_curve_sampled_coal(qba_ctx *ctx, int n, int n_dis,
   if (int rc = qba_set_device(ctx)) return rc;
   M.ps = (const QbaProgramSet *)ctx->prog_dev[n];
   return with_n(n, [&](auto k) { return qba_launch_mc_coal<decltype(k)::value>(ctx, M); });
+}
+
+// The curve call on a network that loses packets: the
+// _adv curve call's arguments, then the network word, checked right after the
+// policy word and before ctx.
+extern "C" int qba_montecarlo_curve_sampled_net(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
+                                                const uint32_t *counts, int n_counts, uint32_t flip_q16, int32_t *out,
+                                                qba_stream stream, uint32_t adv, uint32_t net) {
+  const char *who = "qba_montecarlo_curve_sampled_net";
+  QbaMc M{who, nullptr, seed_base, n_inst, n_dis, out, (hipStream_t)stream, {}, 1, {}, adv, 1, {}, 0u, net};
+  const char *bad = bad_flip(flip_q16);
+  if (!bad) bad = qba_adv_bad(adv);
+  if (!bad) bad = qba_net_bad(net);
+  if (int rc = qba_mc_curve_check(who, ctx, n, n_dis, n_inst, counts, n_counts, out, &M.counts, bad)) return rc;
+  if (flip_q16) M.noise = qba_noise_of(flip_q16);
+  if (int rc = need_program(ctx, n, who)) return rc;
+  if (n_inst == 0) return QBA_OK;
+  if (int rc = qba_set_device(ctx)) return rc;
+  M.ps = (const QbaProgramSet *)ctx->prog_dev[n];
+  return with_n(n, [&](auto k) { return qba_launch_mc_net<decltype(k)::value>(ctx, M); });
 }
 
 // The curve call under every scenario of a list: one

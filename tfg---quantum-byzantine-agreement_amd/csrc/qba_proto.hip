@@ -18,6 +18,7 @@
 //             rows into the same masks (mc_entry, qba_proto_rounds.h)
 #include "qba_proto_adv.h"  // the entry points' policy check and launches; the kernels here keep qba_proto_rounds.h
 #include "qba_proto_coal.h"  // ... and the coalition word's check and launch
+#include "qba_proto_net.h"   // ... and the network word's
 
 namespace {
 
@@ -356,6 +357,27 @@ extern "C" int qba_montecarlo_curve_lists_coal(qba_ctx *ctx, int n, int n_dis, u
   return launch_chunks(ctx, n_inst, [&](int64_t first, dim3 grid) {
     qba_launch_mc_coal_lists(grid, lds, (hipStream_t)stream, n, n_dis, seed_base, first, n_inst, lists, ld,
                              inst_stride, out, cv, adv, coal);
+  });
+}
+
+// qba_montecarlo_curve_lists_adv on a network that loses packets (DESIGN.md
+// section 13.11): the kernel of qba_proto_net.hip, in that call's LDS layout.
+// The network word is checked right after the policy word.
+extern "C" int qba_montecarlo_curve_lists_net(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
+                                              const uint32_t *counts, int n_counts, const uint8_t *lists, uint64_t ld,
+                                              uint64_t inst_stride, int32_t *out, qba_stream stream, uint32_t adv,
+                                              uint32_t net) {
+  const char *who = "qba_montecarlo_curve_lists_net";
+  QbaMcCounts cv;
+  const char *bad = qba_adv_bad(adv);
+  int rc = qba_mc_curve_check(who, ctx, n, n_dis, n_inst, counts, n_counts, out, &cv, bad ? bad : qba_net_bad(net));
+  if (rc || (rc = lists_check(who, n, n_inst, cv.c[cv.n - 1], lists, ld, inst_stride)) || n_inst == 0) return rc;
+  const int G = n + 1, w = 1 << qba_nq(n);
+  const size_t lds = (size_t)(PROTO_S_WORDS + ((proto_box_words(G, w) + 3) & ~3) + mc_acc_words(G, w)) *
+                     sizeof(uint32_t);  // the _adv curve call's: <= 37024 B
+  return launch_chunks(ctx, n_inst, [&](int64_t first, dim3 grid) {
+    qba_launch_mc_net_lists(grid, lds, (hipStream_t)stream, n, n_dis, seed_base, first, n_inst, lists, ld,
+                            inst_stride, out, cv, adv, net);
   });
 }
 

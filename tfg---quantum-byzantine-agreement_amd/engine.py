@@ -531,6 +531,47 @@ class Engine:
              (C.c_uint32 * len(cs))(*cs), len(cs), _ptr(lists), ld, stride, _ptr(out), self.stream(), adv, coal)
         return out
 
+    # -- the curve on a network that loses packets (qba_montecarlo_curve_*_net) -----
+    @staticmethod
+    def _check_net(net) -> int:
+        """A network word (None: 0, the perfect network) checked on the host."""
+        from .montecarlo import check_net
+        return 0 if net is None else check_net(net)
+
+    def montecarlo_curve_sampled_net(self, n: int, n_dishonest: int, seed_base: int, n_inst: int, counts,
+                                     out: Optional[torch.Tensor] = None, flip_q16: int = 0,
+                                     adversary: Optional[int] = None, net: Optional[int] = None) -> torch.Tensor:
+        """montecarlo_curve_sampled on lossy links
+        (qba_montecarlo_curve_sampled_net): the same rows layout, the dishonest
+        parties under the policy ``adversary`` (None: the reference's 0xF) and
+        packets lost as the network word ``net`` says (montecarlo.net; None or
+        0: the perfect network, the rows of the ``adversary`` call)."""
+        self._check_n(n)
+        cs = self._check_curve(n, n_dishonest, n_inst, counts)
+        flip = self._check_flip(flip_q16)
+        adv = self._check_adversary(0xF if adversary is None else adversary)
+        word = self._check_net(net)
+        self.prepare(n)
+        out = self._rows_out(n, n_inst, out, len(cs))
+        call("qba_montecarlo_curve_sampled_net", self.ctx, n, n_dishonest, _u64(seed_base), n_inst,
+             (C.c_uint32 * len(cs))(*cs), len(cs), flip, _ptr(out), self.stream(), adv, word)
+        return out
+
+    def montecarlo_curve_lists_net(self, n: int, n_dishonest: int, seed_base: int, lists, counts,
+                                   out: Optional[torch.Tensor] = None, adversary: Optional[int] = None,
+                                   net: Optional[int] = None) -> torch.Tensor:
+        """The same from injected lists (qba_montecarlo_curve_lists_net), as
+        montecarlo_curve_lists takes them."""
+        self._check_n(n)
+        cs = self._check_curve(n, n_dishonest, 0, counts)
+        adv = self._check_adversary(0xF if adversary is None else adversary)
+        word = self._check_net(net)
+        lists, n_inst, ld, stride = self._mc_lists(n, lists, cs[-1])
+        out = self._rows_out(n, n_inst, out, len(cs))
+        call("qba_montecarlo_curve_lists_net", self.ctx, n, n_dishonest, _u64(seed_base), n_inst,
+             (C.c_uint32 * len(cs))(*cs), len(cs), _ptr(lists), ld, stride, _ptr(out), self.stream(), adv, word)
+        return out
+
     # -- a grid of scenarios per checkpoint in one pass (qba_montecarlo_sweep_*) ----
     SWEEP_MAX = 16  # QBA_MC_SWEEP_MAX
 

@@ -61,6 +61,12 @@ host forms): a second word, built by
 lieutenants withhold accepted packets from the honest ones and inject them in a
 late round, padded with each other's tuples.  :class:`CoalitionParty` is the
 definition; ``None`` and ``0`` are "no coalition".
+
+Lossy links (``net=word`` on :func:`run`, :func:`curve` and their host forms;
+DESIGN.md section 13.11): a word built by :func:`net` under which a packet in
+flight is lost with probability ``drop_q16 / 65536``, decided per packet by
+the pure function :func:`net_lost`.  :class:`NetParty` is the definition;
+``None`` and ``0`` are the perfect network.
 """
 from __future__ import annotations
 
@@ -605,9 +611,156 @@ def coalition_party(adv: int, coal: int, base=None):
     return type(f"CoalitionParty_{adv:x}_{coal:x}", bases, {"adv": adv, "coal": coal})
 
 
+# ---------------------------------------------------------------------------
+# Lossy links
+# ---------------------------------------------------------------------------
+NET_TAG = 0x4E455457  # word 3 of every loss counter
+NET_CMD = 1 << 16
+_NET_VALID = 0x0001FFFF
+
+
+def check_net(word) -> int:
+    """``word`` as an int when it is a valid network word (0: the perfect
+    network); QbaError otherwise (a reserved bit, or cmd with drop_q16 == 0)."""
+    try:
+        w = int(word)
+    except (TypeError, ValueError):
+        raise QbaError(f"net must be an integer network word, not {word!r}") from None
+    if w < 0 or w & ~_NET_VALID:
+        raise QbaError(f"network word {w:#x} sets a reserved bit")
+    if w & NET_CMD and not w & 0xFFFF:
+        raise QbaError(f"network word {w:#x} sets the cmd field with drop_q16 == 0")
+    return w
+
+
+def net(drop_q16: int, cmd: bool = False) -> int:
+    """The network word: a packet on a lossy link is lost with probability
+    ``drop_q16 / 65536``; the lieutenant-to-lieutenant links are lossy, and with
+    ``cmd`` the commander's links of epoch 0 too."""
+    k = int(drop_q16)
+    if not 0 <= k <= 0xFFFF:
+        raise QbaError("drop_q16 must be in [0, 65535]")
+    return check_net(k | (NET_CMD if cmd else 0))
+
+
+def parse_net(text) -> int:
+    """``K`` or ``K:cmd`` (K decimal or ``0x`` hex) as a checked network word."""
+    cmd = False
+    if isinstance(text, str):
+        head, sep, tail = text.partition(":")
+        if sep and tail != "cmd":
+            raise QbaError(f"net {text!r}: only ':cmd' may follow drop_q16")
+        cmd = bool(sep)
+        try:
+            text = int(head, 0)
+        except ValueError:
+            raise QbaError(f"net {text!r}: drop_q16 is a number (0x... or decimal)") from None
+    try:
+        return net(text, cmd)
+    except (TypeError, ValueError):
+        raise QbaError(f"net {text!r}: drop_q16 is a number (0x... or decimal)") from None
+
+
+def net_lost(key: int, epoch: int, src: int, dest: int, seq: int, drop_q16: int) -> bool:
+    """Whether the packet ``seq`` that ``src`` hands to the link towards ``dest``
+    in epoch ``epoch`` of the instance keyed ``key`` is lost: the low 16 bits of
+    word ``seq & 3`` of ``philox4x32((epoch, src | dest << 8, seq >> 2, NET_TAG),
+    key)`` are below ``drop_q16``.  A function of the packet alone."""
+    x = philox4x32((epoch, src | dest << 8, seq >> 2, NET_TAG), int(key) & MASK64)[seq & 3]
+    return (x & 0xFFFF) < int(drop_q16)
+
+
+class NetLost:
+    """What a lieutenant receives in place of a lost commander packet."""
+
+
+class NetParty(AdversaryParty):
+    """AdversaryParty on the network the word ``net`` describes (a class
+    attribute: :func:`net_party` makes the subclass of a pair of words).  The
+    specification of the ``_net`` kernels; with ``net == 0`` it is
+    AdversaryParty.
+
+    Every ``send`` counts, takes the next ``seq`` of its (epoch, dest) and is
+    then handed over or, on a lossy link, lost as :func:`net_lost` says of
+    ``(self.seed, epoch, rank, dest, seq)`` -- ``self.seed`` is the instance key
+    under :func:`run_host`.  The epoch is 0 during comm_broadcast and ``rnd``
+    while a packet of round ``rnd`` is processed.  In LocalWorld a lost
+    commander packet travels as a marker (v = -1) that the lieutenant's ``recv``
+    turns into :class:`NetLost`, so that nobody blocks; the lieutenant then
+    skips step 3a.  A lost lieutenant packet is simply not sent."""
+
+    net = 0
+    _LOST_V = -1  # the marker's v; an order, also a traitor's, is >= 0
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self._epoch = 0
+        self._seq: Dict[tuple, int] = {}
+
+    def lossy(self, dest: int) -> bool:
+        """Whether this rank's link towards ``dest`` loses packets."""
+        return bool(self.net & 0xFFFF) and (self.rank >= 2 or bool(self.net & NET_CMD))
+
+    def send(self, dest, P, v, L):
+        e = self._epoch
+        seq = self._seq.get((e, dest), 0)
+        self._seq[(e, dest)] = seq + 1
+        if self.lossy(dest) and net_lost(self.seed, e, self.rank, dest, seq, self.net & 0xFFFF):
+            self.stats.sent += 1  # the sender cannot tell
+            return self.lose(dest, P, v, L, e, seq)
+        super().send(dest, P, v, L)
+
+    def lose(self, dest, P, v, L, epoch, seq):
+        """The packet is lost (an observation seam).  Only a commander's loss
+        leaves a trace: the marker its receiver is waiting for."""
+        if self.rank == 1:
+            head = np.array([-1, self._LOST_V, 0], dtype=np.int64)
+            self.comm.Isend([head, protocol._dt(self.comm)], dest=dest, tag=1).Wait()
+            self.comm.Isend([np.zeros(0, np.int64), protocol._dt(self.comm)], dest=dest, tag=2).Wait()
+
+    def recv(self, src):
+        P, v, L = super().recv(src)
+        return (NetLost, v, L) if v == self._LOST_V else (P, v, L)
+
+    def comm_broadcast(self):
+        self._epoch = 0
+        if self.rank <= 1 or not self.net & NET_CMD:
+            return super().comm_broadcast()
+        self.wire.clear()
+        P, v, L = self.recv(1)
+        if P is NetLost:
+            return
+        if self.add_own_and_check(P, v, L):
+            self.Vi.add(v)
+            self.lieu_broadcast(P, v, L)
+
+    def lieu_receive(self, P, v, L, rnd, pre=None):
+        self._epoch = rnd
+        super().lieu_receive(P, v, L, rnd, pre)
+
+
+def net_party(adv: int, net: int, base=None):
+    """The :class:`NetParty` subclass of a policy word and a network word, for
+    the ``party_cls`` seam of :func:`run_host`; ``base`` as in
+    :func:`adversary_party`, or an observing :class:`NetParty` subclass."""
+    adv, net = check_adversary(adv), check_net(net)
+    if base is not None and issubclass(base, NetParty):
+        bases = (base,)
+    else:
+        bases = (NetParty,) if base in (None, CountParty, AdversaryParty) else (NetParty, base)
+    return type(f"NetParty_{adv:x}_{net:x}", bases, {"adv": adv, "net": net})
+
+
+def _no_net(net, what: str) -> None:
+    """ValueError when ``net`` is a non-zero network word: ``what`` is not built for one."""
+    if net is not None and check_net(net):
+        raise ValueError(f"{what} is not built for a lossy network (net={int(net):#x})")
+
+
 def run_host(n: int, sizeL: int, n_dishonest: int, n_inst: int, seed_base: int, engine, lists=None,
              party_cls=None, rng_factory: Optional[Callable] = None, flip_q16: int = 0,
-             adversary: Optional[int] = None, coalition: Optional[int] = None) -> np.ndarray:
+             adversary: Optional[int] = None, coalition: Optional[int] = None,
+             net: Optional[int] = None) -> np.ndarray:
     """The specification of qba_protocol_batched: CountParty under
     ``protocol.run_local`` (LocalWorld's barrier-epoch delivery: a round's inbox
     is everything sent in the previous epoch, in (source, sequence) order,
@@ -631,10 +784,20 @@ def run_host(n: int, sizeL: int, n_dishonest: int, n_inst: int, seed_base: int, 
     under ``adversary``, or the reference's rule); ``None`` and ``0`` are no
     coalition and call what is called without the argument; ``party_cls`` may
     then be an observing :class:`CoalitionParty` subclass.
+
+    ``net=word``: packets are lost in flight (:class:`NetParty` under
+    ``adversary``, or the reference's rule); ``None`` and ``0`` are the perfect
+    network and call what is called without the argument; ``party_cls`` may
+    then be an observing :class:`NetParty` subclass.  Not with a coalition.
     """
     flip = _check_flip(flip_q16)
     coal = 0 if coalition is None else check_coalition(coalition)
-    if coal:
+    lossy = 0 if net is None else check_net(net)
+    if lossy:
+        if coal:
+            _no_net(lossy, "a coalition")
+        party_cls = net_party(ADV_REFERENCE if adversary is None else adversary, lossy, party_cls)
+    elif coal:
         party_cls = coalition_party(ADV_REFERENCE if adversary is None else adversary, coal, party_cls)
     elif adversary is not None:
         party_cls = adversary_party(adversary, party_cls)
@@ -896,7 +1059,8 @@ def masks_from_lists(n: int, lists) -> dict:
 
 def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, packed: bool = True,
         batch: int = 4096, path: str = "tables", tally: bool = False, failures: int = 0, flip_q16: int = 0,
-        adversary: Optional[int] = None, explain: int = 0, coalition: Optional[int] = None) -> dict:
+        adversary: Optional[int] = None, explain: int = 0, coalition: Optional[int] = None,
+        net: Optional[int] = None) -> dict:
     """``runs`` independent instances on the device, ``batch`` at a time, batch
     at offset ``off`` under key ``seed + off``; only the result rows are copied
     to the host.  Returns :func:`summarize` of all rows.
@@ -932,9 +1096,20 @@ def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, pack
     ``coalition=word`` (``path="fused"`` only, without ``explain``): the
     dishonest parties collude (:func:`coalition`); the decisions go through the
     coalition kernel as a curve of the one checkpoint ``sizeL``.  ``None`` and
-    ``0`` call what is called without the argument."""
+    ``0`` call what is called without the argument.
+
+    ``net=word`` (``path="fused"`` only, without ``explain`` or ``coalition``):
+    packets are lost in flight (:func:`net`); the decisions go through the
+    lossy-network kernel as a curve of the one checkpoint ``sizeL``.  ``None``
+    and ``0`` call what is called without the argument."""
     if path not in ("tables", "fused", "tables_noisy"):
         raise ValueError("path is 'tables', 'fused' or 'tables_noisy'")
+    if net is not None and check_net(net):
+        if path != "fused":
+            _no_net(net, f"path={path!r}")
+        return curve(n, [sizeL], n_dishonest, runs, seed, engine, batch=batch, tally=tally, failures=failures,
+                     flip_q16=flip_q16, adversary=adversary, explain=explain, coalition=coalition,
+                     net=net)[int(sizeL)]
     if coalition is not None and check_coalition(coalition):
         if path != "fused" or explain:
             raise ValueError("coalition needs path='fused' and no explain: the tables path and the trace "
@@ -962,13 +1137,14 @@ def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, pack
 
 
 def curve_host(n: int, counts, n_dishonest: int, n_inst: int, seed_base: int, engine, lists=None,
-               flip_q16: int = 0, adversary: Optional[int] = None, coalition: Optional[int] = None) -> np.ndarray:
+               flip_q16: int = 0, adversary: Optional[int] = None, coalition: Optional[int] = None,
+               net: Optional[int] = None) -> np.ndarray:
     """The specification of the curve calls: the stack of :func:`run_host` at
     each count of ``counts``, int32 [len(counts), n_inst, out_words(n)].
     Injected ``lists`` [n_inst, n+1, >= max(counts)] are truncated to
     ``[:, :, :c]`` for the count c.  ``flip_q16`` as in :func:`run_host` (the
-    flips of entry e are the same at every count), ``adversary`` and
-    ``coalition``."""
+    flips of entry e are the same at every count), ``adversary``,
+    ``coalition`` and ``net`` (a packet's loss does not depend on the count)."""
     counts = [int(c) for c in counts]
     li = None if lists is None else np.asarray(lists)
     noise = {"flip_q16": flip_q16} if flip_q16 else {}
@@ -976,6 +1152,8 @@ def curve_host(n: int, counts, n_dishonest: int, n_inst: int, seed_base: int, en
         noise["adversary"] = adversary
     if coalition is not None:
         noise["coalition"] = coalition
+    if net is not None:
+        noise["net"] = net
     rows = [run_host(n, c, n_dishonest, n_inst, seed_base, engine, lists=None if li is None else li[:, :, :c],
                      **noise)
             for c in counts]
@@ -984,7 +1162,7 @@ def curve_host(n: int, counts, n_dishonest: int, n_inst: int, seed_base: int, en
 
 def curve(n: int, counts, n_dishonest: int, runs: int, seed: int, engine, batch: int = 4096, tally: bool = False,
           failures: int = 0, flip_q16: int = 0, adversary: Optional[int] = None, explain: int = 0,
-          coalition: Optional[int] = None) -> dict:
+          coalition: Optional[int] = None, net: Optional[int] = None) -> dict:
     """The failure curve over sizeL: ``runs`` instances, ``batch`` at a time as
     :func:`run` keys them, each decided at every sizeL of the strictly
     increasing ``counts`` by one montecarlo_curve_sampled call per batch.
@@ -994,18 +1172,27 @@ def curve(n: int, counts, n_dishonest: int, runs: int, seed: int, engine, batch:
     ``adversary`` and ``explain`` as there (one trace call per checkpoint).
     ``coalition=word`` (not with ``explain``): one
     montecarlo_curve_sampled_coal call per batch instead; ``None`` and ``0``
-    call what is called without it."""
+    call what is called without it.  ``net=word`` (not with ``explain`` or
+    ``coalition``): one montecarlo_curve_sampled_net call per batch instead;
+    ``None`` and ``0`` call what is called without it."""
     counts = [int(c) for c in counts]
     noise = {"flip_q16": _check_flip(flip_q16)} if flip_q16 else {}
     if adversary is not None:
         noise["adversary"] = check_adversary(adversary)
     coal = 0 if coalition is None else check_coalition(coalition)
+    lossy = 0 if net is None else check_net(net)
+    if lossy and coal:
+        _no_net(lossy, "a coalition")
+    if lossy and explain:
+        _no_net(lossy, "explain (the trace kernels)")
     if coal and explain:
         raise ValueError("explain is not built for a coalition: the trace kernels do not collude")
     if tally or failures:
         engine._check_curve(n, n_dishonest, 0, counts)  # before any device buffer: an empty list has no slice
 
     def decide(key, b, **into):
+        if lossy:
+            return engine.montecarlo_curve_sampled_net(n, n_dishonest, key, b, counts, net=lossy, **into, **noise)
         if coal:
             return engine.montecarlo_curve_sampled_coal(n, n_dishonest, key, b, counts, coalition=coal, **into,
                                                         **noise)
@@ -1046,7 +1233,7 @@ def sweep_host(n: int, counts, scenarios, n_inst: int, seed_base: int, engine, l
 
 
 def sweep(n: int, counts, scenarios, runs: int, seed: int, engine, batch: int = 4096, tally: bool = False,
-          failures: int = 0, flip_q16: int = 0, explain: int = 0) -> dict:
+          failures: int = 0, flip_q16: int = 0, explain: int = 0, net: Optional[int] = None) -> dict:
     """:func:`curve` under every scenario ``(n_dishonest, word)`` of
     ``scenarios`` at once: ``runs`` instances, ``batch`` at a time as
     :func:`run` keys them, each sampled and distilled once and decided at every
@@ -1055,7 +1242,9 @@ def sweep(n: int, counts, scenarios, runs: int, seed: int, engine, batch: int = 
     n_dishonest, word): summary}`` in slice order, checkpoints outermost; each
     summary is that of ``curve(..., n_dishonest, adversary=word)`` at that
     sizeL.  ``tally``, ``failures``, ``flip_q16`` and ``explain`` as there (one
-    trace call per slice).  Duplicate scenarios would share a key: ValueError."""
+    trace call per slice).  Duplicate scenarios would share a key: ValueError.
+    ``net`` is taken only to be refused when it is a non-zero network word."""
+    _no_net(net, "a sweep")
     counts = [int(c) for c in counts]
     sc = _scenarios(n, scenarios)
     if len(set(sc)) != len(sc):

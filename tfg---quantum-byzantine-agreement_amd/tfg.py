@@ -114,6 +114,11 @@ def _args(argv):
                          "starve_late) or a coalition word (montecarlo.coalition): they withhold packets from honest "
                          "lieutenants and inject them in a late round, padded with each other's tuples; implies "
                          "--fused; the summary lines end in collude=0xWORD; not with --sweep, --explain or --tables")
+    ap.add_argument("--drop", default=None, metavar="K[:cmd]",
+                    help="with --runs: every lieutenant-to-lieutenant packet is lost in flight with probability "
+                         "K / 65536 (K decimal or 0x hex; montecarlo.net), with :cmd the commander's packets too; "
+                         "implies --fused; the summary lines end in drop=K/65536 [cmd]; not with --collude, --sweep, "
+                         "--explain or --tables")
     ap.add_argument("--sweep", default=None, metavar="K:POLICY,...",
                     help="with --runs: decide every instance under each of these scenarios in one pass per batch "
                          "(montecarlo.sweep; at most 16, and 32 lines with --curve): K traitors following POLICY "
@@ -173,6 +178,18 @@ def _args(argv):
             a.collude = montecarlo.parse_coalition(a.collude)
         except montecarlo.QbaError as e:
             ap.error(f"--collude: {e}")
+        a.fused = True
+    if a.drop is not None:
+        if a.runs is None:
+            ap.error("--drop needs --runs")
+        if a.collude is not None or a.sweep is not None or a.explain or a.tables:
+            ap.error("--drop: not with --collude, --sweep, --explain or --tables (the coalition, sweep, trace and "
+                     "tables paths are not built for a lossy network)")
+        from . import montecarlo
+        try:
+            a.drop = montecarlo.parse_net(a.drop)
+        except montecarlo.QbaError as e:
+            ap.error(f"--drop: {e}")
         a.fused = True
     if a.sweep is not None:
         if a.runs is None:
@@ -318,6 +335,9 @@ def _montecarlo(a, eng, size_l) -> int:
     if a.collude is not None:
         how["coalition"] = a.collude
         noise += f" collude={a.collude:#x}"
+    if a.drop is not None:
+        how["net"] = a.drop
+        noise += f" drop={a.drop & 0xFFFF}/65536" + (" cmd" if a.drop >> 16 else "")
     if a.sweep is not None:
         grid = montecarlo.sweep(a.parties, a.curve if a.curve is not None else [size_l], a.sweep, a.runs, seed, eng,
                                 batch=a.batch, **how)

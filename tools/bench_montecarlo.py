@@ -61,6 +61,16 @@ instances x n = 7 x sizeL = 1e5, 2 dishonest, on one GPU.
       reorder_low (or those of --adversary).  A coalition runs another protocol:
       its times are reported without a verdict, its success counts beside them.
 
+  --drop K[:cmd]  (repeatable) another mode, per --sizeL: the lossy-network
+      call (qba_montecarlo_curve_sampled_net, one checkpoint) at net = 0 -- the
+      rows of the _adv curve call, which is checked: unequal rows are an error
+      -- and at each network word given (drop_q16 = K, with :cmd the
+      commander's packets too), beside that _adv curve call, which is timed
+      first and again last in the same session, under each of the policies
+      reference and reorder_low (or those of --adversary).  A lossy network
+      runs another protocol: its times are reported without a verdict, its
+      success counts beside them.
+
   --trace  another mode, per --sizeL: the montecarlo_trace_sampled call at 16
       and at --instances indices (cap 256, the reference policy word) beside
       montecarlo_sampled(..., adversary=0xF) of the same number of instances --
@@ -134,6 +144,10 @@ def main(argv=None) -> int:
                     help="time the coalition call at coal = 0 and under each of these coalition words beside the "
                          "_adv curve call of one checkpoint, at each --sizeL, under the policies of --adversary "
                          "(default reference and reorder_low); nothing else is measured")
+    ap.add_argument("--drop", action="append", default=None, metavar="K[:cmd]",
+                    help="time the lossy-network call at net = 0 and at each of these network words beside the "
+                         "_adv curve call of one checkpoint, at each --sizeL, under the policies of --adversary "
+                         "(default reference and reorder_low); nothing else is measured")
     ap.add_argument("--trace", action="store_true",
                     help="time montecarlo_trace_sampled at 16 and at --instances indices beside montecarlo_sampled "
                          "with the reference policy word at the same shapes, and the host wall time of trace_host "
@@ -143,6 +157,8 @@ def main(argv=None) -> int:
         ap.error("--trace goes with --sizeL alone")
     if a.collude and (a.trace or a.sweep or a.flip or a.curve or a.tally or a.tables):
         ap.error("--collude goes with --sizeL and --adversary alone")
+    if a.drop and (a.collude or a.trace or a.sweep or a.flip or a.curve or a.tally or a.tables):
+        ap.error("--drop goes with --sizeL and --adversary alone")
     if a.sweep and (a.flip or a.tally or a.tables or a.adversary):
         ap.error("--sweep goes with --sizeL or --curve alone")
     if a.adversary and (a.flip or a.curve or a.tally or a.tables):
@@ -151,7 +167,9 @@ def main(argv=None) -> int:
         ap.error("--tables needs --flip and goes with neither --curve nor --tally")
 
     eng = importlib.import_module(f"{PKG}.engine").Engine(0)
-    if a.collude:
+    if a.drop:
+        lines = [json.dumps(_measure_drop(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
+    elif a.collude:
         lines = [json.dumps(_measure_collude(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
     elif a.trace:
         lines = [json.dumps(_measure_trace(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
@@ -360,6 +378,48 @@ def _measure_collude(a, eng, size_l) -> dict:
         r["no_coalition_ranges_overlap"] = not (z["min_ms"] > hi or z["max_ms"] < lo)
         r["no_coalition_slower"] = z["min_ms"] > hi
         r["no_coalition_faster"] = z["max_ms"] < lo
+        res["policies"][policy] = r
+    return res
+
+
+def _measure_drop(a, eng, size_l) -> dict:
+    """--drop: per policy, the _adv curve call of one checkpoint first and last, the lossy-network call at
+    net = 0 (equal rows, or an error) and at each network word between them."""
+    import torch
+    mc = importlib.import_module(f"{PKG}.montecarlo")
+    n, nd, inst = a.parties, a.dishonest, a.instances
+    res = {"config": {"n": n, "sizeL": size_l, "dishonest": nd, "instances": inst, "seed": a.seed,
+                      "device": torch.cuda.get_device_name(0)}, "policies": {}}
+    for policy in a.adversary or ["reference", "reorder_low"]:
+        adv = mc.parse_adversary(policy)
+        rows = eng.montecarlo_curve_sampled(n, nd, a.seed, inst, [size_l], adversary=adv)
+        ref = rows.clone()
+        parent = lambda: eng.montecarlo_curve_sampled(n, nd, a.seed, inst, [size_l], rows, adversary=adv)  # noqa: E731
+        r = {"word": f"{adv:#x}", "adv_curve_call": _events(parent, a.warmup, a.repeats), "nets": {}}
+        r["adv_curve_call"]["successes"] = int(ref[0, :, 0].sum())
+        for name in ["0"] + [w for w in a.drop if mc.parse_net(w)]:
+            word = mc.parse_net(name)
+            t = _events(lambda: eng.montecarlo_curve_sampled_net(n, nd, a.seed, inst, [size_l], rows, adversary=adv,
+                                                                 net=word), a.warmup, a.repeats)
+            t["word"] = f"{word:#x}"
+            t["rows_equal_adv_curve_call"] = bool(torch.equal(rows, ref))
+            if not word and not t["rows_equal_adv_curve_call"]:
+                raise SystemExit(f"net = 0 does not give the _adv curve call's rows (n={n}, sizeL={size_l}, {policy})")
+            t["successes"] = int(rows[0, :, 0].sum())
+            t["empty_vi_runs"] = int((rows[0, :, 2] != 0).sum())
+            r["nets"][name] = t
+        r["adv_curve_call_again"] = _events(parent, a.warmup, a.repeats)
+        first, last = r["adv_curve_call"], r["adv_curve_call_again"]
+        base = min(first["median_ms"], last["median_ms"])
+        r["adv_curve_call_spread_at_median"] = abs(first["median_ms"] - last["median_ms"]) / base
+        for t in r["nets"].values():
+            t["over_adv_curve_call_at_median"] = t["median_ms"] / base
+        z = r["nets"]["0"]
+        lo, hi = min(first["min_ms"], last["min_ms"]), max(first["max_ms"], last["max_ms"])
+        # a verdict only for net = 0 (equal rows), and only where the min-max ranges do not overlap
+        r["perfect_network_ranges_overlap"] = not (z["min_ms"] > hi or z["max_ms"] < lo)
+        r["perfect_network_slower"] = z["min_ms"] > hi
+        r["perfect_network_faster"] = z["max_ms"] < lo
         res["policies"][policy] = r
     return res
 
