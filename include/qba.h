@@ -785,6 +785,51 @@ QBA_API int qba_montecarlo_curve_lists_net(qba_ctx *ctx, int n_parties, int n_di
                                            const uint8_t *lists_dev, uint64_t ld, uint64_t inst_stride,
                                            int32_t *out_dev, qba_stream stream, uint32_t adv, uint32_t net);
 
+/* A grid of (n_dishonest, adv, net) scenarios per checkpoint in one pass
+ * (DESIGN.md section 13.12): the sweep calls with a network word in every
+ * scenario.  The two calls are qba_montecarlo_curve_sampled_net /
+ * qba_montecarlo_curve_lists_net deciding every instance at every checkpoint
+ * under every scenario scen_host[0 .. n_scen): the entries are sampled (or
+ * read) and distilled once, and at each checkpoint the rounds run once per
+ * scenario on the same masks.  Instance i at checkpoint j under scenario s
+ * writes 4 + 5*(n+1) int32 at
+ *   out_dev + (((int64_t)j * n_scen + s) * n_instances + i) * (4 + 5*(n+1)),
+ * word for word (status included) the row the _net curve call writes at
+ * counts_host[j] with scenario s's n_dishonest, adv and net; at net == 0 that
+ * is also the sweep call's slice.  out_dev is
+ * [n_counts][n_scen][n_instances][4 + 5*(n+1)], contiguous, and
+ * qba_montecarlo_tally takes it as n_counts * n_scen slices.
+ * Under one key the lists, the traitor draw and the commander's order are the
+ * same in every scenario, and a packet's loss word does not depend on
+ * drop_q16: a packet lost at drop_q16 = K is lost at every K' >= K, so
+ * scenarios that differ in drop_q16 alone lose nested sets of the packets they
+ * have in common.
+ * Checked in this order, each QBA_EINVAL: n_parties; the checkpoint list as
+ * the curve calls check it; flip_q16 (sampled form); scen_host not NULL and
+ * 1 <= n_scen <= QBA_MC_GRID_MAX; n_counts * n_scen <= QBA_MC_CURVE_MAX; then
+ * scenario 0, 1, ...: n_dishonest in [0, n_parties], then adv as the _adv calls
+ * check it, then net as the _net calls check it (the message names the first
+ * bad scenario by index and the field); then ctx, n_instances and out_dev as
+ * those calls.  Equal scenarios are legal and give equal slices.  Both host
+ * arrays travel by value in the kernel arguments and may be reused when the
+ * call returns.  Asynchronous on `stream`, allocate and copy nothing, legal in
+ * a stream capture.  The launch shape of the sampled form is
+ * qba_montecarlo_curve_shape's.  Specification: montecarlo.grid_host. */
+#define QBA_MC_GRID_MAX 16
+typedef struct {
+  int32_t n_dishonest;
+  uint32_t adv;
+  uint32_t net;
+} qba_mc_grid_scenario;
+QBA_API int qba_montecarlo_grid_sampled(qba_ctx *ctx, int n_parties, uint64_t seed_base, int64_t n_instances,
+                                        const uint32_t *counts_host, int n_counts,
+                                        const qba_mc_grid_scenario *scen_host, int n_scen, uint32_t flip_q16,
+                                        int32_t *out_dev, qba_stream stream);
+QBA_API int qba_montecarlo_grid_lists(qba_ctx *ctx, int n_parties, uint64_t seed_base, int64_t n_instances,
+                                      const uint32_t *counts_host, int n_counts,
+                                      const qba_mc_grid_scenario *scen_host, int n_scen, const uint8_t *lists_dev,
+                                      uint64_t ld, uint64_t inst_stride, int32_t *out_dev, qba_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,11 @@ class Scenario(C.Structure):
     _fields_ = [("n_dishonest", C.c_int32), ("adv", C.c_uint32)]
 
 
+class GridScenario(C.Structure):
+    """qba_mc_grid_scenario: one (n_dishonest, policy word, network word) of a grid call."""
+    _fields_ = [("n_dishonest", C.c_int32), ("adv", C.c_uint32), ("net", C.c_uint32)]
+
+
 # name -> argtypes (restype is int unless listed in _RESTYPE)
 SIGNATURES = {
     "qba_last_error": [],
@@ -95,6 +100,10 @@ SIGNATURES = {
                                      C.c_int, C.c_uint32, _p, _p],
     "qba_montecarlo_sweep_lists": [_p, C.c_int, _u64, _i64, C.POINTER(C.c_uint32), C.c_int, C.POINTER(Scenario),
                                    C.c_int, _p, _u64, _u64, _p, _p],
+    "qba_montecarlo_grid_sampled": [_p, C.c_int, _u64, _i64, C.POINTER(C.c_uint32), C.c_int, C.POINTER(GridScenario),
+                                    C.c_int, C.c_uint32, _p, _p],
+    "qba_montecarlo_grid_lists": [_p, C.c_int, _u64, _i64, C.POINTER(C.c_uint32), C.c_int, C.POINTER(GridScenario),
+                                  C.c_int, _p, _u64, _u64, _p, _p],
     "qba_noise_apply_batched": [_p, C.c_int, _u64, _i64, _u64, C.c_uint32, _p, _u64, _u64, _p],
     "qba_montecarlo_curve_shape": [C.c_int, C.POINTER(C.c_int), _pi64, C.POINTER(C.c_int)],
     "qba_montecarlo_program_shape": [_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),

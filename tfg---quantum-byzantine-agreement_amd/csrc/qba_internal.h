@@ -280,6 +280,17 @@ struct QbaMcScen {
 int qba_mc_sweep_check(const char *who, qba_ctx *ctx, int n, int64_t n_inst, const uint32_t *counts, int n_counts,
                        const qba_mc_scenario *scen, int n_scen, const char *bad_flip, const void *out,
                        QbaMcCounts *cv, QbaMcScen *sv);
+// The scenarios of a grid call, by value in the
+// kernel arguments as the sweep's are
+struct QbaMcGrid {
+  qba_mc_grid_scenario s[QBA_MC_GRID_MAX];
+  int n;
+};
+// The sweep calls' envelope for qba_montecarlo_grid_sampled / _lists: a
+// scenario is checked n_dishonest, adv, then net; fills `cv` and `gv`
+int qba_mc_grid_check(const char *who, qba_ctx *ctx, int n, int64_t n_inst, const uint32_t *counts, int n_counts,
+                      const qba_mc_grid_scenario *scen, int n_scen, const char *bad_flip, const void *out,
+                      QbaMcCounts *cv, QbaMcGrid *gv);
 
 static inline int qba_nq(int n) {  // ceil(log2(n+1)), tfg.py:317
   int q = 0;

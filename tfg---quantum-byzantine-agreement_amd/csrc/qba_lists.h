@@ -56,6 +56,7 @@ struct QbaMc {
   QbaMcScen scen;  // read by the sweep kernel alone (qba_montecarlo_sweep_sampled), which takes no n_dis / adv
   uint32_t coal;   // the coalition word, read by the coalition kernel alone (qba_montecarlo_curve_sampled_coal)
   uint32_t net;    // the network word, read by the lossy-network kernel alone (qba_montecarlo_curve_sampled_net)
+  QbaMcGrid grid;  // read by the grid kernel alone (qba_montecarlo_grid_sampled), which takes no n_dis / adv / net
 };
 
 template <int NP>
@@ -88,6 +89,9 @@ void qba_mc_coal_shape_n(int *waves, int64_t *lds, int *wgs);
 // the curve under a policy and a network word, through the lossy-network kernel (qba_mc_net_inst.hip)
 template <int NP>
 int qba_launch_mc_net(qba_ctx *ctx, const QbaMc &M);
+// the curve under every scenario of M.grid, through the grid kernel (qba_mc_grid_inst.hip)
+template <int NP>
+int qba_launch_mc_grid(qba_ctx *ctx, const QbaMc &M);
 // qba_montecarlo_shape, or (curve) qba_montecarlo_curve_shape
 template <int NP>
 void qba_mc_shape_n(int curve, int *waves, int64_t *lds, int *wgs);

@@ -254,6 +254,26 @@ extern "C" int qba_montecarlo_sweep_sampled(qba_ctx *ctx, int n, uint64_t seed_b
   return with_n(n, [&](auto k) { return qba_launch_mc_sweep<decltype(k)::value>(ctx, M); });
 }
 
+// The sweep call with a network word in every scenario (DESIGN.md section
+// 13.12): one pass over the entries, the lossy-network rounds once per
+// checkpoint and scenario.  Checked in the sweep call's order, a scenario
+// n_dishonest, adv, then net (qba_mc_grid_check).
+extern "C" int qba_montecarlo_grid_sampled(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst,
+                                           const uint32_t *counts, int n_counts, const qba_mc_grid_scenario *scen,
+                                           int n_scen, uint32_t flip_q16, int32_t *out, qba_stream stream) {
+  const char *who = "qba_montecarlo_grid_sampled";
+  QbaMc M{who, nullptr, seed_base, n_inst, 0, out, (hipStream_t)stream, {}, 1, {}, 0u, 0, {}, 0u, 0u, {}};
+  if (int rc = qba_mc_grid_check(who, ctx, n, n_inst, counts, n_counts, scen, n_scen, bad_flip(flip_q16), out,
+                                 &M.counts, &M.grid))
+    return rc;
+  if (flip_q16) M.noise = qba_noise_of(flip_q16);
+  if (int rc = need_program(ctx, n, who)) return rc;
+  if (n_inst == 0) return QBA_OK;
+  if (int rc = qba_set_device(ctx)) return rc;
+  M.ps = (const QbaProgramSet *)ctx->prog_dev[n];
+  return with_n(n, [&](auto k) { return qba_launch_mc_grid<decltype(k)::value>(ctx, M); });
+}
+
 // The flips of the noisy Monte-Carlo calls into lists in the layout of
 // qba_sample_check_batched, in place (qba_noise.hip); its argument checks,
 // after flip_q16.  Needs no program: it samples nothing.

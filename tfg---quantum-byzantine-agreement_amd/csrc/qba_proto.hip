@@ -249,6 +249,35 @@ int qba_mc_sweep_check(const char *who, qba_ctx *ctx, int n, int64_t n_inst, con
   return QBA_OK;
 }
 
+int qba_mc_grid_check(const char *who, qba_ctx *ctx, int n, int64_t n_inst, const uint32_t *counts, int n_counts,
+                      const qba_mc_grid_scenario *scen, int n_scen, const char *bad_flip, const void *out,
+                      QbaMcCounts *cv, QbaMcGrid *gv) {
+  std::string at;  // "scenario i: what": the envelope reports the first bad scenario by its index
+  const char *bad = bad_counts(counts, n_counts);
+  if (!bad) bad = bad_flip;
+  if (!bad) {
+    if (!scen) bad = "scen is NULL";
+    else if (n_scen < 1 || n_scen > QBA_MC_GRID_MAX) bad = "n_scen must be in [1, 16]";
+    else if (n_counts * n_scen > QBA_MC_CURVE_MAX) bad = "n_counts * n_scen must be <= 32";
+  }
+  for (int s = 0; !bad && s < n_scen; ++s) {
+    const char *b = scen[s].n_dishonest < 0 || scen[s].n_dishonest > n ? "n_dishonest must be in [0, n_parties]"
+                                                                       : qba_adv_bad(scen[s].adv);
+    if (!b) b = qba_net_bad(scen[s].net);
+    if (!b) continue;
+    at = "scenario " + std::to_string(s) + ": " + b;
+    bad = at.c_str();
+  }
+  if (int rc = qba_mc_check(who, ctx, n, 0, bad, n_inst, out)) return rc;
+  *cv = QbaMcCounts{};
+  for (int j = 0; j < n_counts; ++j) cv->c[j] = counts[j];
+  cv->n = n_counts;
+  *gv = QbaMcGrid{};
+  for (int s = 0; s < n_scen; ++s) gv->s[s] = scen[s];
+  gv->n = n_scen;
+  return QBA_OK;
+}
+
 // The injected rows of the two list calls hold `need` entries (the count, or
 // the last checkpoint) per row without overlapping.
 static int lists_check(const char *who, int n, int64_t n_inst, uint64_t need, const uint8_t *lists, uint64_t ld,
@@ -398,5 +427,26 @@ extern "C" int qba_montecarlo_sweep_lists(qba_ctx *ctx, int n, uint64_t seed_bas
   return launch_chunks(ctx, n_inst, [&](int64_t first, dim3 grid) {
     qba_launch_mc_sweep_lists(grid, lds, (hipStream_t)stream, n, seed_base, first, n_inst, lists, ld, inst_stride,
                               out, cv, sv);
+  });
+}
+
+// qba_montecarlo_curve_lists_net under every scenario of a list at every
+// checkpoint: the kernel of qba_proto_grid.hip, in
+// that call's LDS layout.
+extern "C" int qba_montecarlo_grid_lists(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst,
+                                         const uint32_t *counts, int n_counts, const qba_mc_grid_scenario *scen,
+                                         int n_scen, const uint8_t *lists, uint64_t ld, uint64_t inst_stride,
+                                         int32_t *out, qba_stream stream) {
+  const char *who = "qba_montecarlo_grid_lists";
+  QbaMcCounts cv;
+  QbaMcGrid gv;
+  int rc = qba_mc_grid_check(who, ctx, n, n_inst, counts, n_counts, scen, n_scen, nullptr, out, &cv, &gv);
+  if (rc || (rc = lists_check(who, n, n_inst, cv.c[cv.n - 1], lists, ld, inst_stride)) || n_inst == 0) return rc;
+  const int G = n + 1, w = 1 << qba_nq(n);
+  const size_t lds = (size_t)(PROTO_S_WORDS + ((proto_box_words(G, w) + 3) & ~3) + mc_acc_words(G, w)) *
+                     sizeof(uint32_t);  // <= 37024 B
+  return launch_chunks(ctx, n_inst, [&](int64_t first, dim3 grid) {
+    qba_launch_grid_lists(grid, lds, (hipStream_t)stream, n, seed_base, first, n_inst, lists, ld, inst_stride, out,
+                          cv, gv);
   });
 }

@@ -60,6 +60,10 @@ inline const char *qba_net_bad(uint32_t net) {
 void qba_launch_mc_net_lists(dim3 grid, size_t lds, hipStream_t stream, int n, int n_dis, uint64_t seed_base,
                              int64_t first, int64_t n_inst, const uint8_t *lists, uint64_t ld, uint64_t inst_stride,
                              int32_t *out, const QbaMcCounts &cv, uint32_t adv, uint32_t net);
+// ... and of qba_proto_grid.hip's (the curve under every scenario of `gv`)
+void qba_launch_grid_lists(dim3 grid, size_t lds, hipStream_t stream, int n, uint64_t seed_base, int64_t first,
+                           int64_t n_inst, const uint8_t *lists, uint64_t ld, uint64_t inst_stride, int32_t *out,
+                           const QbaMcCounts &cv, const QbaMcGrid &gv);
 
 namespace {
 

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import resource
-from ._lib import KIND_NOTQ, KIND_Q, MAX_PARTIES, QbaError, Scenario, call, lib
+from ._lib import KIND_NOTQ, KIND_Q, MAX_PARTIES, GridScenario, QbaError, Scenario, call, lib
 
 
 def _ptr(t: torch.Tensor) -> C.c_void_p:
@@ -640,6 +640,70 @@ class Engine:
         if isinstance(out, torch.Tensor) and out.is_contiguous() and tuple(out.shape) == (k, s, n_inst, words):
             out = out.view(k * s, n_inst, words)
         return self._rows_out(n, n_inst, out, k * s).view(k, s, n_inst, words)
+
+    # -- a grid of (traitors, policy, network) scenarios in one pass (qba_montecarlo_grid_*) --
+    GRID_MAX = 16  # QBA_MC_GRID_MAX
+
+    @classmethod
+    def _check_grid(cls, n: int, n_inst: int, counts, scenarios):
+        """The argument check of the two montecarlo_grid_* methods: the
+        checkpoints as a list of ints and the scenarios as a list of
+        ``(n_dishonest, word, net)``."""
+        cs = cls._check_curve(n, 0, n_inst, counts)
+        try:
+            sc = [(int(k), word, net) for k, word, net in scenarios]
+        except (TypeError, ValueError):
+            raise QbaError("scenarios must be a sequence of (n_dishonest, policy word, network word) triples") from None
+        if not 1 <= len(sc) <= cls.GRID_MAX:
+            raise QbaError(f"between 1 and {cls.GRID_MAX} scenarios, not {len(sc)}")
+        if len(cs) * len(sc) > cls.CURVE_MAX:
+            raise QbaError(f"len(counts) * len(scenarios) must be <= {cls.CURVE_MAX}, not {len(cs) * len(sc)}")
+        for i, (k, word, net) in enumerate(sc):
+            if not 0 <= k <= n:
+                raise QbaError(f"scenario {i}: n_dishonest={k} outside [0, {n}]")
+            if word is None:
+                raise QbaError(f"scenario {i}: the policy word is None (0xF is the reference's traitor)")
+            try:
+                sc[i] = (k, cls._check_adversary(word), cls._check_net(net))
+            except QbaError as e:
+                raise QbaError(f"scenario {i}: {e}") from None
+        return cs, sc
+
+    @staticmethod
+    def _grid_array(sc):
+        return (GridScenario * len(sc))(*(GridScenario(k, word, net) for k, word, net in sc))
+
+    def montecarlo_grid_sampled(self, n: int, seed_base: int, n_inst: int, counts, scenarios,
+                                out: Optional[torch.Tensor] = None, flip_q16: int = 0) -> torch.Tensor:
+        """The n_inst instances of montecarlo_curve_sampled_net decided at every
+        count of ``counts`` under every scenario ``(n_dishonest, word, net)`` of
+        ``scenarios`` (at most 16, and at most 32 slices in all) in one pass
+        over their entries (qba_montecarlo_grid_sampled): int32 [len(counts),
+        len(scenarios), n_inst, 4 + 5*(n+1)], slice (j, s) word for word
+        montecarlo_curve_sampled_net(..., adversary=word, net=net)[j] with that
+        n_dishonest.  ``flip_q16`` as there."""
+        self._check_n(n)
+        cs, sc = self._check_grid(n, n_inst, counts, scenarios)
+        flip = self._check_flip(flip_q16)
+        self.prepare(n)
+        out = self._sweep_out(n, n_inst, out, len(cs), len(sc))
+        call("qba_montecarlo_grid_sampled", self.ctx, n, _u64(seed_base), n_inst, (C.c_uint32 * len(cs))(*cs),
+             len(cs), self._grid_array(sc), len(sc), flip, _ptr(out), self.stream())
+        return out
+
+    def montecarlo_grid_lists(self, n: int, seed_base: int, lists, counts, scenarios,
+                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The same from injected lists (qba_montecarlo_grid_lists), as
+        montecarlo_curve_lists takes them: slice (j, s) is
+        montecarlo_curve_lists_net(..., adversary=word, net=net)[j] with that
+        n_dishonest."""
+        self._check_n(n)
+        cs, sc = self._check_grid(n, 0, counts, scenarios)
+        lists, n_inst, ld, stride = self._mc_lists(n, lists, cs[-1])
+        out = self._sweep_out(n, n_inst, out, len(cs), len(sc))
+        call("qba_montecarlo_grid_lists", self.ctx, n, _u64(seed_base), n_inst, (C.c_uint32 * len(cs))(*cs),
+             len(cs), self._grid_array(sc), len(sc), _ptr(lists), ld, stride, _ptr(out), self.stream())
+        return out
 
     @classmethod
     def montecarlo_curve_shape(cls, n: int) -> Tuple[int, int, int]:

@@ -67,6 +67,12 @@ DESIGN.md section 13.11): a word built by :func:`net` under which a packet in
 flight is lost with probability ``drop_q16 / 65536``, decided per packet by
 the pure function :func:`net_lost`.  :class:`NetParty` is the definition;
 ``None`` and ``0`` are the perfect network.
+
+A grid (:func:`grid`, ``Engine.montecarlo_grid_sampled`` /
+``montecarlo_grid_lists``) is the sweep with a
+network word in every scenario, ``(n_dishonest, word, net)``: one pass, and
+along ``drop_q16`` the loss decisions are nested.  :func:`grid_host` is its
+specification.
 """
 from __future__ import annotations
 
@@ -1260,6 +1266,70 @@ def sweep(n: int, counts, scenarios, runs: int, seed: int, engine, batch: int = 
         return engine.montecarlo_sweep_sampled(n, key, b, counts, sc, **into, **noise).view(k, b, out_words(n))
     ex = (keys, flip_q16, explain) if explain else None
     return dict(zip(keys, _batches(n, k, runs, batch, seed, engine, decide, tally, failures, ex)))
+
+
+def _grid_scenarios(n: int, scenarios) -> list:
+    """``scenarios`` as a list of ``(n_dishonest, checked policy word, checked
+    network word)``; an error names the scenario by its index."""
+    try:
+        sc = [(int(k), word, net) for k, word, net in scenarios]
+    except (TypeError, ValueError):
+        raise QbaError("scenarios must be a sequence of (n_dishonest, policy word, network word) triples") from None
+    for i, (k, word, net) in enumerate(sc):
+        if not 0 <= k <= n:
+            raise QbaError(f"scenario {i}: n_dishonest={k} outside [0, {n}]")
+        try:
+            sc[i] = (k, check_adversary(word), check_net(net))
+        except QbaError as e:
+            raise QbaError(f"scenario {i}: {e}") from None
+    return sc
+
+
+def grid_host(n: int, counts, scenarios, n_inst: int, seed_base: int, engine, lists=None,
+              flip_q16: int = 0) -> np.ndarray:
+    """The specification of the grid calls: the stack
+    of :func:`curve_host` under each scenario ``(n_dishonest, word, net)`` of
+    ``scenarios``, int32 [len(counts), len(scenarios), n_inst, out_words(n)].
+
+    Under one key the lists, the traitor draw and the commander's order are the
+    same in every scenario (:func:`sweep_host`), and :func:`net_lost` compares
+    a word that does not depend on ``drop_q16``: a packet lost at ``drop_q16 =
+    K`` is lost at every ``K' >= K``.  Scenarios that differ in ``drop_q16``
+    alone therefore lose nested sets of the packets they have in common."""
+    sc = _grid_scenarios(n, scenarios)
+    rows = [curve_host(n, counts, k, n_inst, seed_base, engine, lists=lists, flip_q16=flip_q16, adversary=word,
+                       net=net)
+            for k, word, net in sc]
+    if not rows:
+        return np.zeros((len(list(counts)), 0, n_inst, out_words(n)), np.int32)
+    return np.stack(rows, axis=1)
+
+
+def grid(n: int, counts, scenarios, runs: int, seed: int, engine, batch: int = 4096, tally: bool = False,
+         failures: int = 0, flip_q16: int = 0) -> dict:
+    """:func:`curve` under every scenario ``(n_dishonest, word, net)`` of
+    ``scenarios`` at once: ``runs`` instances, ``batch`` at a time as
+    :func:`run` keys them, each sampled and distilled once and decided at every
+    sizeL of ``counts`` under every scenario by one montecarlo_grid_sampled call
+    per batch (at most 16 scenarios and 32 slices).  Returns ``{(sizeL,
+    n_dishonest, word, net): summary}`` in slice order, checkpoints outermost;
+    each summary is that of ``curve(..., n_dishonest, adversary=word, net=net)``
+    at that sizeL.  ``tally``, ``failures`` and ``flip_q16`` as there.  There is
+    no ``explain``: the trace kernels are not built for a lossy network.
+    Duplicate scenarios would share a key: ValueError."""
+    counts = [int(c) for c in counts]
+    sc = _grid_scenarios(n, scenarios)
+    if len(set(sc)) != len(sc):
+        raise ValueError("duplicate scenarios: every (n_dishonest, word, net) may be given once")
+    noise = {"flip_q16": _check_flip(flip_q16)} if flip_q16 else {}
+    engine._check_grid(n, 0, counts, sc)  # before any device buffer: an empty grid has no slice
+    k = len(counts) * len(sc)
+    keys = [(c, kd, word, net) for c in counts for kd, word, net in sc]
+
+    def decide(key, b, out=None):
+        into = {} if out is None else {"out": out}
+        return engine.montecarlo_grid_sampled(n, key, b, counts, sc, **into, **noise).view(k, b, out_words(n))
+    return dict(zip(keys, _batches(n, k, runs, batch, seed, engine, decide, tally, failures, None)))
 
 
 # ---------------------------------------------------------------------------

@@ -49,6 +49,7 @@ def _sizes(text: str):
 
 
 SWEEP_MAX = 16  # scenarios of one --sweep run (QBA_MC_SWEEP_MAX)
+GRID_MAX = 16  # items of one --grid run (QBA_MC_GRID_MAX)
 EXPLAIN_CAP = 1024  # events kept per rank of an --explain transcript (the rest are counted)
 
 
@@ -63,6 +64,22 @@ def _scenarios(text: str, n_dishonest: int, montecarlo) -> list:
         out.append((int(k), montecarlo.parse_adversary(pol.strip())))
     if len(set(out)) != len(out):
         raise ValueError("a scenario is given twice")
+    return out
+
+
+def _grid_items(text: str, n_dishonest: int, montecarlo) -> list:
+    """--grid's SCENARIO[@DROP[:cmd]],... as [(K, policy word, network word)]:
+    SCENARIO as --sweep takes it, DROP[:cmd] as --drop does; absent, the
+    perfect network."""
+    out = []
+    for item in (x.strip() for x in text.split(",") if x.strip()):
+        scen, sep, drop = item.partition("@")
+        sc = _scenarios(scen, n_dishonest, montecarlo)
+        if len(sc) != 1 or (sep and not drop.strip()):
+            raise ValueError(f"{item!r} is not SCENARIO[@DROP[:cmd]]")
+        out.append(sc[0] + (montecarlo.parse_net(drop.strip()) if sep else 0,))
+    if len(set(out)) != len(out):
+        raise ValueError("an item is given twice")
     return out
 
 
@@ -124,6 +141,13 @@ def _args(argv):
                          "(montecarlo.sweep; at most 16, and 32 lines with --curve): K traitors following POLICY "
                          "(as --adversary takes it); a bare POLICY uses the positional nDishonest, a bare K the "
                          "reference policy; one summary line per sizeL and scenario; implies --fused")
+    ap.add_argument("--grid", default=None, metavar="SCENARIO[@DROP[:cmd]],...",
+                    help="with --runs: decide every instance under each of these items in one pass per batch "
+                         "(montecarlo.grid; at most 16, and 32 lines with --curve): SCENARIO as --sweep takes it "
+                         "(K:POLICY, a bare K or a bare POLICY) on the network DROP[:cmd] as --drop takes it (absent: "
+                         "the perfect network), e.g. 2@0,2@0x0100,2@0x1000:cmd,2:reorder_low@0x0400; one summary "
+                         "line per sizeL and item; implies --fused; not with --sweep, --drop, --adversary, "
+                         "--collude, --explain or --tables")
     ap.add_argument("--quiet", action="store_true", help="print only the outcome")
     ap.add_argument("--timing", action="store_true", help="print the wall time of the run")
     ap.add_argument("--wire", action="store_true",
@@ -203,6 +227,22 @@ def _args(argv):
             ap.error(f"--sweep: {e}")
         if not 1 <= len(a.sweep) <= SWEEP_MAX or len(a.sweep) * len(a.curve or [0]) > CURVE_MAX:
             ap.error(f"--sweep: between 1 and {SWEEP_MAX} scenarios, and at most {CURVE_MAX} lines with --curve")
+    if a.grid is not None:
+        if a.runs is None:
+            ap.error("--grid needs --runs")
+        if a.sweep is not None or a.drop is not None or a.adversary is not None or a.collude is not None or \
+                a.explain or a.tables:
+            ap.error("--grid: not with --sweep, --drop, --adversary (name the policy and the network per item), "
+                     "--collude, --explain or --tables (the coalition, trace and tables paths are not built for a "
+                     "lossy network)")
+        from . import montecarlo
+        try:
+            a.grid = _grid_items(a.grid, a.nDishonest, montecarlo)
+        except (ValueError, montecarlo.QbaError) as e:
+            ap.error(f"--grid: {e}")
+        if not 1 <= len(a.grid) <= GRID_MAX or len(a.grid) * len(a.curve or [0]) > CURVE_MAX:
+            ap.error(f"--grid: between 1 and {GRID_MAX} items, and at most {CURVE_MAX} lines with --curve")
+        a.fused = True
     return a
 
 
@@ -319,7 +359,9 @@ def _montecarlo(a, eng, size_l) -> int:
     """--runs R: R independent count-mode instances decided on the device
     (montecarlo.run); one summary line, or with --curve one per sizeL
     (montecarlo.curve), or with --sweep one per sizeL and scenario
-    (montecarlo.sweep), each the line of the --adversary run of that scenario."""
+    (montecarlo.sweep), each the line of the --adversary run of that scenario,
+    or with --grid one per sizeL and item (montecarlo.grid), each the line of
+    the --adversary --drop run of that item."""
     from . import montecarlo
     seed = secrets.randbits(62) if a.seed is None else a.seed
     t0 = time.perf_counter()
@@ -338,7 +380,13 @@ def _montecarlo(a, eng, size_l) -> int:
     if a.drop is not None:
         how["net"] = a.drop
         noise += f" drop={a.drop & 0xFFFF}/65536" + (" cmd" if a.drop >> 16 else "")
-    if a.sweep is not None:
+    if a.grid is not None:
+        grid = montecarlo.grid(a.parties, a.curve if a.curve is not None else [size_l], a.grid, a.runs, seed, eng,
+                               batch=a.batch, **how)
+        points = {(c, k, f"{noise} adversary={word:#x}"
+                   + (f" drop={net & 0xFFFF}/65536" + (" cmd" if net >> 16 else "") if net else "")): s
+                  for (c, k, word, net), s in grid.items()}
+    elif a.sweep is not None:
         grid = montecarlo.sweep(a.parties, a.curve if a.curve is not None else [size_l], a.sweep, a.runs, seed, eng,
                                 batch=a.batch, **how)
         points = {(c, k, f"{noise} adversary={word:#x}"): s for (c, k, word), s in grid.items()}
@@ -349,7 +397,7 @@ def _montecarlo(a, eng, size_l) -> int:
                                          path="tables_noisy" if a.tables else "fused" if a.fused else "tables",
                                          **how)}
     for c, s in points.items():
-        c, dis, tail = c if a.sweep is not None else (c, a.nDishonest, noise)
+        c, dis, tail = c if a.sweep is not None or a.grid is not None else (c, a.nDishonest, noise)
         print(f"Runs: {s['runs']} Successes: {s['successes']} Rate: {s['rate']:.6f} "
               f"(n={a.parties}, sizeL={c}, dishonest={dis}, empty-V_i runs={s['empty_vi_runs']}){tail}")
         if a.failures:

@@ -53,6 +53,16 @@ instances x n = 7 x sizeL = 1e5, 2 dishonest, on one GPU.
       the same grid, the S timed as one interval; the rows of the two are
       compared at the timed shape.  One JSON line per --sweep and shape.
 
+  --grid SCENARIO[@DROP[:cmd]],...  (repeatable) another mode, per --sizeL and
+      per --curve: one montecarlo_grid_sampled call over the grid of items
+      (SCENARIO as --sweep takes it, on the network DROP[:cmd]; tfg --grid's
+      grammar) against the S montecarlo_curve_sampled_net calls of the same
+      grid, the S timed as one interval; the rows of the two are compared at
+      the timed shape, and the success counts of every slice are reported.  A
+      call holds at most 32 slices: a grid past that (nine items on a ladder of
+      four) goes in the fewest grid calls, timed as one interval ("grid_calls").
+      One JSON line per --grid and shape.
+
   --collude NAME|0xHEX  (repeatable) another mode, per --sizeL: the coalition
       call (qba_montecarlo_curve_sampled_coal, one checkpoint) at coal = 0 -- the
       rows of the _adv curve call, which is checked -- and under each coalition
@@ -140,6 +150,9 @@ def main(argv=None) -> int:
     ap.add_argument("--sweep", action="append", default=None, metavar="K:POLICY,...",
                     help="time one sweep call over these scenarios against the separate curve calls with a policy, "
                          "at each --sizeL (one checkpoint) or each --curve; repeatable; nothing else is measured")
+    ap.add_argument("--grid", action="append", default=None, metavar="SCENARIO[@DROP[:cmd]],...",
+                    help="time one grid call over these items against the separate lossy-network curve calls, at "
+                         "each --sizeL (one checkpoint) or each --curve; repeatable; nothing else is measured")
     ap.add_argument("--collude", action="append", default=None, metavar="NAME|0xHEX",
                     help="time the coalition call at coal = 0 and under each of these coalition words beside the "
                          "_adv curve call of one checkpoint, at each --sizeL, under the policies of --adversary "
@@ -159,6 +172,8 @@ def main(argv=None) -> int:
         ap.error("--collude goes with --sizeL and --adversary alone")
     if a.drop and (a.collude or a.trace or a.sweep or a.flip or a.curve or a.tally or a.tables):
         ap.error("--drop goes with --sizeL and --adversary alone")
+    if a.grid and (a.sweep or a.drop or a.collude or a.trace or a.flip or a.tally or a.tables or a.adversary):
+        ap.error("--grid goes with --sizeL or --curve alone")
     if a.sweep and (a.flip or a.tally or a.tables or a.adversary):
         ap.error("--sweep goes with --sizeL or --curve alone")
     if a.adversary and (a.flip or a.curve or a.tally or a.tables):
@@ -167,7 +182,10 @@ def main(argv=None) -> int:
         ap.error("--tables needs --flip and goes with neither --curve nor --tally")
 
     eng = importlib.import_module(f"{PKG}.engine").Engine(0)
-    if a.drop:
+    if a.grid:
+        shapes = [[s] for s in (a.sizeL or [])] + [sorted({int(c) for c in text.split(",")}) for text in a.curve or []]
+        lines = [json.dumps(_measure_grid(a, eng, counts, text)) for text in a.grid for counts in shapes or [[100_000]]]
+    elif a.drop:
         lines = [json.dumps(_measure_drop(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
     elif a.collude:
         lines = [json.dumps(_measure_collude(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
@@ -261,6 +279,53 @@ def _measure_sweep(a, eng, counts, text) -> dict:
     res["separate_over_sweep_at_median"] = s["median_ms"] / c["median_ms"]
     # faster only where the min-max ranges do not overlap
     res["sweep_faster"] = c["max_ms"] < s["min_ms"]
+    res["separate_faster"] = s["max_ms"] < c["min_ms"]
+    return res
+
+
+def _measure_grid(a, eng, counts, text) -> dict:
+    """--grid: one grid call against the separate lossy-network curve calls of its items."""
+    import torch
+    tfg = importlib.import_module(f"{PKG}.tfg")
+    mc = importlib.import_module(f"{PKG}.montecarlo")
+    n, inst = a.parties, a.instances
+    scen = tfg._grid_items(text, a.dishonest, mc)
+    # a call holds at most 32 slices: a grid past that goes in the fewest calls, near-equal, timed as one interval
+    calls = -(-len(counts) * len(scen) // eng.CURVE_MAX)
+    if len(counts) * -(-len(scen) // calls) > eng.CURVE_MAX:
+        calls += 1
+    per = -(-len(scen) // calls)
+    parts = [scen[i:i + per] for i in range(0, len(scen), per)]
+    outs = [eng.montecarlo_grid_sampled(n, a.seed, inst, counts, part) for part in parts]
+    single = torch.empty((len(scen), len(counts), inst, outs[0].shape[-1]), dtype=torch.int32, device=eng.device)
+
+    def grid():
+        for part, out in zip(parts, outs):
+            eng.montecarlo_grid_sampled(n, a.seed, inst, counts, part, out)
+
+    def separate():
+        for s, (k, word, net) in enumerate(scen):
+            eng.montecarlo_curve_sampled_net(n, k, a.seed, inst, counts, single[s], adversary=word, net=net)
+
+    def equal():
+        return bool(torch.equal(torch.cat(outs, dim=1), single.transpose(0, 1)))
+
+    separate()
+    torch.cuda.synchronize()
+    res = {"config": {"n": n, "counts": counts, "scenarios": [[k, f"{word:#x}", f"{net:#x}"] for k, word, net in scen],
+                      "instances": inst, "seed": a.seed, "device": torch.cuda.get_device_name(0),
+                      "slices": len(counts) * len(scen), "grid_calls": len(parts),
+                      "entries_grid": counts[-1] * len(parts), "entries_separate": counts[-1] * len(scen)},
+           "rows_equal_separate_calls": equal()}
+    res["separate_montecarlo_curve_sampled_net"] = _events(separate, a.warmup, a.repeats)
+    res["grid_montecarlo_grid_sampled"] = _events(grid, a.warmup, a.repeats)
+    res["rows_equal_separate_calls"] = res["rows_equal_separate_calls"] and equal()
+    # successes of every slice, from the grid's rows: [checkpoint][item]
+    res["successes"] = torch.cat(outs, dim=1)[..., 0].sum(dim=2).tolist()
+    s, c = res["separate_montecarlo_curve_sampled_net"], res["grid_montecarlo_grid_sampled"]
+    res["separate_over_grid_at_median"] = s["median_ms"] / c["median_ms"]
+    # faster only where the min-max ranges do not overlap
+    res["grid_faster"] = c["max_ms"] < s["min_ms"]
     res["separate_faster"] = s["max_ms"] < c["min_ms"]
     return res
 
