@@ -576,6 +576,50 @@ QBA_API int qba_montecarlo_trace_lists(qba_ctx *ctx, int n_parties, uint64_t see
                                        uint64_t ld, uint64_t inst_stride, int32_t *rows_dev, int32_t *counts_dev,
                                        uint32_t *events_dev, qba_stream stream);
 
+/* The transcript on a network that loses packets:
+ * the two trace calls above with the network word `net` of the _net curve
+ * calls appended after `stream`.  They re-run the instances as
+ * qba_montecarlo_curve_sampled_net / qba_montecarlo_curve_lists_net decide them
+ * at the one checkpoint `count`, and write the rows of those calls word for
+ * word, with the events above and two more:
+ *   QBA_EV_SLOT_LOST   the `slot` of a SEND event whose packet was handed to a
+ *                      lossy link and lost in flight.  Such a send counts in
+ *                      the row's sent and advances the link's seq; it takes no
+ *                      mailbox slot, so the next send to that destination in
+ *                      that round gets the slot this one would have had.  29
+ *                      is below 30: SEND events with slot < 30 are still the
+ *                      row's sent.  code is the drawn action or QBA_EV_HONEST,
+ *                      len and pkt those of the packet as handed over, after a
+ *                      traitor's mutation.  Under cmd the commander's round-0
+ *                      SEND carries it too.
+ *   QBA_EV_NO_PACKET   the `code` of the one RECV event of a lieutenant whose
+ *                      commander packet was lost: round 0, peer 1, slot 0,
+ *                      len 0, pkt 0.  Neither an accept nor a reject, as in the
+ *                      row.  A lost lieutenant-to-lieutenant packet leaves no
+ *                      event at the receiver.
+ * A send that action 0 suppresses stays QBA_EV_SLOT_MUTED: it is not handed to
+ * the link and seq does not move.  Every other event is bit for bit what the
+ * calls above define, and with net == 0 the calls write their rows, counts and
+ * events word for word.
+ * The checks are those calls' in their order, with net checked as the _net
+ * curve calls check it right after adv (before n_idx and idx_dev).
+ * Asynchronous on `stream`, allocate and copy nothing, legal in a stream
+ * capture; the launch shape of the sampled form is qba_montecarlo_shape's.
+ * Specification: montecarlo.trace_net_host. */
+#define QBA_EV_SLOT_LOST 29u
+#define QBA_EV_NO_PACKET 6u
+QBA_API int qba_montecarlo_trace_sampled_net(qba_ctx *ctx, int n_parties, uint64_t seed_base,
+                                             const int64_t *idx_dev, int64_t n_idx, const int64_t *n_match_dev,
+                                             uint64_t count, int n_dishonest, uint32_t adv, uint32_t flip_q16,
+                                             int64_t cap, int32_t *rows_dev, int32_t *counts_dev,
+                                             uint32_t *events_dev, qba_stream stream, uint32_t net);
+QBA_API int qba_montecarlo_trace_lists_net(qba_ctx *ctx, int n_parties, uint64_t seed_base, const int64_t *idx_dev,
+                                           int64_t n_idx, const int64_t *n_match_dev, uint64_t count,
+                                           int n_dishonest, uint32_t adv, uint32_t flip_q16, int64_t cap,
+                                           const uint8_t *lists_dev, uint64_t ld, uint64_t inst_stride,
+                                           int32_t *rows_dev, int32_t *counts_dev, uint32_t *events_dev,
+                                           qba_stream stream, uint32_t net);
+
 /* ---- (A5-A8) checks, exact-order mode (bit-exact protocol parity) --------------- */
 /* isQCorrList = {k : Li[k] != Lc[k]} (tfg.py:327) as ascending indices.
  * *count_host receives the number found; at most `cap` are written. Synchronous. */

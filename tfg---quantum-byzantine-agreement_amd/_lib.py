@@ -113,6 +113,10 @@ SIGNATURES = {
                                      _p, _p, _p],
     "qba_montecarlo_trace_lists": [_p, C.c_int, _u64, _p, _i64, _p, _u64, C.c_int, C.c_uint32, C.c_uint32, _i64, _p,
                                    _u64, _u64, _p, _p, _p, _p],
+    "qba_montecarlo_trace_sampled_net": [_p, C.c_int, _u64, _p, _i64, _p, _u64, C.c_int, C.c_uint32, C.c_uint32, _i64,
+                                         _p, _p, _p, _p, C.c_uint32],
+    "qba_montecarlo_trace_lists_net": [_p, C.c_int, _u64, _p, _i64, _p, _u64, C.c_int, C.c_uint32, C.c_uint32, _i64,
+                                       _p, _u64, _u64, _p, _p, _p, _p, C.c_uint32],
     "qba_isq_indices": [_p, _p, _p, _u64, _p, _i64, _pi64, _p],
     "qba_select_eq": [_p, _p, _i64, _p, _u64, _i64, _p, _pi64, _p],
     "qba_isq_indices_host": [_p, _p, _p, _u64, _p, _i64, _pi64, _p],

@@ -763,6 +763,88 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64, NW * 64)))
 #endif
 
 // ---------------------------------------------------------------------------
+// qba_k_nettrace_sampled: qba_k_trace_sampled with the rounds on a network
+// that loses packets (proto_rounds_nettrace, qba_proto_nettrace.h; DESIGN.md
+// section 13.13): the same slots, idx / n_match handling, outputs and launch
+// shape, and the network word of qba_k_mc_net_sampled, a scalar.  A text of its
+// own, seen by qba_mc_nettrace_inst.hip alone.
+// ---------------------------------------------------------------------------
+#if defined(QBA_MC_NETTRACE_INST)
+#include "qba_proto_nettrace.h"
+template <int NP, int SAMP, int NW>
+__global__ void __attribute__((amdgpu_flat_work_group_size(64, NW * 64)))
+    qba_k_nettrace_sampled(const QbaProgramSet *__restrict__ ps, uint64_t seed_base, const int64_t *__restrict__ idx,
+                           int64_t n_idx, const int64_t *__restrict__ n_match, uint32_t count, int n_dis, int nw_run,
+                           int32_t *__restrict__ rows, int32_t *__restrict__ counts, uint32_t *__restrict__ events,
+                           const QbaNoise nz, uint32_t adv, uint32_t cap, uint32_t net) {
+  using C = QCfg<NP>;
+  constexpr int ND = CF<NP>::ND;
+  extern __shared__ __align__(16) uint64_t lds[];
+  const uint64_t *pat, *apat, *thr;
+  const uint32_t *pl;
+  uint32_t *waves = qba_stage<NP, 1, SAMP, NW * 64>(ps, lds, pat, apat, thr, pl);
+  __syncthreads();
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = (int)__lane_id();
+  if (wv >= nw_run) return;  // tables larger than the shape was compiled for: fewer waves have room
+  uint32_t *mine = waves + (size_t)wv * (qba_mc_wave_lds(C::G, C::W) / sizeof(uint32_t));
+  ProtoShared &S = *reinterpret_cast<ProtoShared *>(mine);
+  uint32_t *box = mine + PROTO_S_WORDS;
+  int64_t lim = n_idx;
+  if (n_match) {
+    const int64_t m = *n_match;
+    lim = m < lim ? (m < 0 ? 0 : m) : lim;
+  }
+  const int64_t stride = (int64_t)gridDim.x * nw_run;
+  for (int64_t j = (int64_t)blockIdx.x * nw_run + wv; j < lim; j += stride) {
+    const uint64_t key = seed_base + (uint64_t)idx[j];
+    const uint32_t k0 = __builtin_amdgcn_readfirstlane((uint32_t)key);
+    const uint32_t k1 = __builtin_amdgcn_readfirstlane((uint32_t)(key >> 32));
+    proto_sync<false>();  // the previous slot's row stores have read S
+    mc_begin(S, box, C::G, C::W, lane);
+    proto_sync<false>();
+    uint32_t seen = 0, bad = 0;
+    if constexpr (SAMP == QBA_S_CLOSED) {
+      // lane l takes pairs l, l + 64, ...: one Philox block, two entries (the
+      // second half of the last block of an odd count stays unused)
+      const uint32_t npair = (count + 1u) >> 1;
+      for (uint32_t p = (uint32_t)lane; p < npair; p += 64u) {
+        const QbaU4 x = qba_philox(p, 0u, 0u, 0u, k0, k1);
+#pragma unroll
+        for (uint32_t h = 0; h < 2; ++h) {
+          if (2u * p + h >= count) break;
+          uint32_t d[ND], D[4] = {0u, 0u, 0u, 0u};
+          qba_closed_half<NP>(h ? x.z : x.x, h ? x.w : x.y, (uint64_t)p, h, k0, k1, pl, d);
+#pragma unroll
+          for (int i = 0; i < ND; ++i) D[i] = d[i];
+          if (nz.steps) qba_noise_d<C::G, C::W>(qba_noise_r(2u * p + h, 0u, k0, k1, nz), D);
+          mc_entry<false>(S, box, D, C::G, C::W, seen, bad);
+        }
+      }
+    } else {
+      for (uint32_t e = (uint32_t)lane; e < count; e += 64u) {
+        uint32_t d[ND], D[4] = {0u, 0u, 0u, 0u};
+        qba_entry_d<NP, SAMP>((uint64_t)e, k0, k1, ps, pat, apat, thr, pl, d);
+#pragma unroll
+        for (int i = 0; i < ND; ++i) D[i] = d[i];
+        if (nz.steps) qba_noise_d<C::G, C::W>(qba_noise_r(e, 0u, k0, k1, nz), D);
+        mc_entry<false>(S, box, D, C::G, C::W, seen, bad);
+      }
+    }
+    mc_flags(box, C::G, C::W, seen, bad);
+    proto_sync<false>();
+    uint32_t st;
+    const uint32_t pnz = mc_finish<false>(S, box, C::G, C::W, lane, st);
+    proto_sync<false>();
+    // lane r <= n owns events[j][r][0 .. cap); the other lanes store nothing
+    uint2 *ev = lane < C::G ? reinterpret_cast<uint2 *>(events) + (j * C::G + lane) * (int64_t)cap : nullptr;
+    proto_rounds_nettrace<false>(S, box, NP, n_dis, key, pnz, st, lane, rows + j * (int64_t)(4 + 5 * C::G), adv, net,
+                                 ev, cap, counts + j * C::G);
+  }
+}
+#endif
+
+// ---------------------------------------------------------------------------
 // qba_k_mc_net_sampled: qba_k_mc_curve_sampled_adv with the rounds on a network
 // that loses packets (proto_rounds_net, qba_proto_net.h; DESIGN.md section
 // 13.11).  The network word is a scalar and the rounds' seq counters are a
@@ -1040,7 +1122,8 @@ static int qba_mc_with_kern(qba_ctx *ctx, bool curve, const F &f) {
 // list kernels stay what they were; the _adv ones by qba_mc_adv_inst.hip, the
 // sweep kernel by qba_mc_sweep_inst.hip, the trace kernel by qba_mc_trace_inst.hip,
 // the coalition kernel by qba_mc_coal_inst.hip, the lossy-network kernel by
-// qba_mc_net_inst.hip, the grid kernel by qba_mc_grid_inst.hip.
+// qba_mc_net_inst.hip, the grid kernel by qba_mc_grid_inst.hip, the
+// lossy-network trace kernel by qba_mc_nettrace_inst.hip.
 #if defined(QBA_MC_TRACE_INST)
 // The trace kernel of (NP, SAMP): the single-count _adv kernels' description
 // (wave count, run_shape) with its own kernel and argument list.
@@ -1179,6 +1262,34 @@ int qba_launch_mc_grid(qba_ctx *ctx, const QbaMc &M) {
     const int nw_run = sh.waves;
     const void *args[] = {&M.ps, &M.seed_base, &M.n_inst, &nw_run, &M.out, &M.counts, &M.noise, &M.grid};
     QBA_HIP(hipLaunchKernel(K::kernel(), dim3(grid), dim3(K::NW * 64), const_cast<void **>(args), sh.lds, M.stream));
+    QBA_HIP(hipGetLastError());
+    return QBA_OK;
+  });
+}
+#elif defined(QBA_MC_NETTRACE_INST)
+// The lossy-network trace kernel of (NP, SAMP): the single-count _adv kernels'
+// description (wave count, run_shape), as the trace kernel's, with its own
+// kernel and argument list.
+template <int NP, int SAMP>
+struct QbaMcNetTraceKern : QbaMcKern<NP, SAMP, false, false, true> {
+  using Base = QbaMcKern<NP, SAMP, false, false, true>;
+  static const void *kernel() { return (const void *)qba_k_nettrace_sampled<NP, SAMP, Base::NW>; }
+};
+template <int NP>
+int qba_launch_mc_nettrace(qba_ctx *ctx, const QbaNetTrace &N) {
+  const QbaTrace &T = N.t;
+  return qba_mc_with_program<NP>(ctx, [&](auto s, size_t tables) -> int {
+    using K = QbaMcNetTraceKern<NP, decltype(s)::value>;
+    const QbaMcShape sh = K::run_shape(tables);
+    if (sh.waves < 1)
+      return qba_fail(QBA_EUNSUPPORTED, std::string(T.who) + ": the program's tables leave no LDS for a wave");
+    if (int rc = lds_allow(K::kernel(), sh.lds)) return rc;
+    const int64_t need = (T.n_idx + sh.waves - 1) / sh.waves, cap = (int64_t)ctx->num_cus * sh.wgs;
+    const int grid = (int)(need < cap ? need : cap);
+    const int nw_run = sh.waves;
+    const void *args[] = {&T.ps,   &T.seed_base, &T.idx,    &T.n_idx,  &T.n_match, &T.count, &T.n_dis, &nw_run,
+                          &T.rows, &T.counts,    &T.events, &T.noise,  &T.adv,     &T.cap,   &N.net};
+    QBA_HIP(hipLaunchKernel(K::kernel(), dim3(grid), dim3(K::NW * 64), const_cast<void **>(args), sh.lds, T.stream));
     QBA_HIP(hipGetLastError());
     return QBA_OK;
   });

@@ -836,6 +836,41 @@ class Engine:
              stride, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), self.stream())
         return out
 
+    # -- ... on a network that loses packets (qba_montecarlo_trace_*_net, section 13.13) --
+    def montecarlo_trace_sampled_net(self, n: int, n_dishonest: int, seed_base: int, indices, count: int,
+                                     cap: int = 256, flip_q16: int = 0, adversary: Optional[int] = None,
+                                     n_match: Optional[torch.Tensor] = None, out=None, net: Optional[int] = None):
+        """montecarlo_trace_sampled on lossy links
+        (qba_montecarlo_trace_sampled_net): the same three outputs, the rows of
+        montecarlo_curve_sampled_net at the one checkpoint ``count`` and the
+        events with montecarlo.EV_SLOT_LOST and montecarlo.EV_NO_PACKET among
+        them.  ``net``: the network word (montecarlo.net; None or 0: the perfect
+        network, the outputs of montecarlo_trace_sampled)."""
+        idx, n_idx, n_match, flip, adv, out = self._trace_args(n, n_dishonest, indices, count, flip_q16, adversary,
+                                                               cap, n_match, out)
+        word = self._check_net(net)
+        self.prepare(n)
+        call("qba_montecarlo_trace_sampled_net", self.ctx, n, _u64(seed_base), _ptr(idx), n_idx,
+             None if n_match is None else _ptr(n_match), count, n_dishonest, adv, flip, int(cap), _ptr(out[0]),
+             _ptr(out[1]), _ptr(out[2]), self.stream(), word)
+        return out
+
+    def montecarlo_trace_lists_net(self, n: int, n_dishonest: int, seed_base: int, indices, lists, count: int,
+                                   cap: int = 256, flip_q16: int = 0, adversary: Optional[int] = None,
+                                   n_match: Optional[torch.Tensor] = None, out=None, net: Optional[int] = None):
+        """The same from injected lists (qba_montecarlo_trace_lists_net), as
+        montecarlo_trace_lists takes them."""
+        idx, n_idx, n_match, flip, adv, out = self._trace_args(n, n_dishonest, indices, count, flip_q16, adversary,
+                                                               cap, n_match, out)
+        word = self._check_net(net)
+        lists, n_lists, ld, stride = self._mc_lists(n, lists, count)
+        if n_lists != n_idx:
+            raise QbaError(f"lists holds {n_lists} instances for {n_idx} indices")
+        call("qba_montecarlo_trace_lists_net", self.ctx, n, _u64(seed_base), _ptr(idx), n_idx,
+             None if n_match is None else _ptr(n_match), count, n_dishonest, adv, flip, int(cap), _ptr(lists), ld,
+             stride, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), self.stream(), word)
+        return out
+
     # -- (A5-A8) count mode -------------------------------------------------------
     def check_counts(self, lists: torch.Tensor, n: int, count: int,
                      counts: Optional[Counts] = None, accumulate: bool = False) -> Counts:

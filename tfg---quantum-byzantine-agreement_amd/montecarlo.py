@@ -1338,6 +1338,8 @@ def grid(n: int, counts, scenarios, runs: int, seed: int, engine, batch: int = 4
 EV_RECV, EV_SEND, EV_DECIDE = 1, 2, 3
 EV_HONEST = 7                       # SEND code of an honest sender
 EV_SLOT_FULL, EV_SLOT_MUTED = 30, 31
+EV_SLOT_LOST = 29                   # SEND slot of a packet lost in flight (section 13.13)
+EV_NO_PACKET = 6                    # RECV code of a lieutenant whose commander packet was lost
 TRACE_CAP_MAX = 4096
 PKT_CLEARED, PKT_EMPTY = 1 << 8, 1 << 13
 VERDICTS = ("accepted", "Cond1", "Cond2", "Cond3", "known v", "wrong length")
@@ -1494,6 +1496,173 @@ def trace_host(n: int, sizeL: int, n_dishonest: int, indices, seed_base: int, en
     return rows, counts, events
 
 
+class TraceNetParty(NetParty):
+    """NetParty that writes down what it does: the
+    events of :class:`TraceParty` on the network the word ``net`` describes,
+    recorded through the ``lose`` and ``recv`` seams NetParty offers.  A send
+    lost in flight is a SEND event with slot :data:`EV_SLOT_LOST`, the packet as
+    it was handed over; it takes no mailbox slot.  A lieutenant whose commander
+    packet was lost records one RECV event with code :data:`EV_NO_PACKET`.  Its
+    draws are NetParty's, draw for draw (trace_net_host's rows are held to
+    ``run_host(..., net=)``), and with ``net == 0`` its events are TraceParty's."""
+
+    sink = None  # {rank: party} of the run, set on the subclass trace_net_host makes
+    verdict = TraceParty.verdict
+    _put = TraceParty._put
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.events = []
+        self._rnd = 0          # 0: the commander's epoch
+        self._inbox = []       # (source, slot, word) of the drained, unprocessed packets
+        self._slots = (None, {})  # the round the send slots belong to, {dest: packets delivered so far}
+        self._lost = False     # whether the last send was lost in flight
+        if self.sink is not None:
+            self.sink[self.rank] = self
+
+    def lose(self, dest, P, v, L, epoch, seq):
+        self._lost = True
+        super().lose(dest, P, v, L, epoch, seq)
+
+    def recv(self, src):
+        P, v, L = super().recv(src)
+        if P is NetLost:
+            self._put(EV_RECV, src, 0, EV_NO_PACKET, 0, 0)
+        else:
+            self._inbox.append((src, sum(1 for s, _, _ in self._inbox if s == src), packet_word(P, v, L)))
+        return P, v, L
+
+    def add_own_and_check(self, P, v, L, pre=None) -> bool:
+        src, slot, word = self._inbox.pop(0)
+        L.add(self.own_tuple(P))
+        code = self.verdict(v, L)
+        ok = code == 0
+        assert ok == self.tables.consistent(v, L), "the verdict and consistent() disagree"
+        self._tally(ok)
+        if ok:  # what lieu_receive tests next (epoch 0: V_i is empty and the one list is the own)
+            code = 4 if v in self.Vi else 5 if len(L) != self._rnd + 1 else 0
+        self._put(EV_RECV, src, slot, code, len(L), word)
+        return ok
+
+    def lieu_receive(self, P, v, L, rnd, pre=None):
+        self._rnd = rnd
+        super().lieu_receive(P, v, L, rnd, pre)
+
+    def send(self, dest, P, v, L):
+        self._lost = False
+        super().send(dest, P, v, L)
+        if self.rank == 1:
+            self._put(EV_SEND, dest, EV_SLOT_LOST if self._lost else 0, EV_HONEST, len(L), packet_word(P, v, L))
+
+    def lieu_broadcast(self, P, v, L):
+        """AdversaryParty.lieu_broadcast, draw for draw, with a SEND event per
+        destination; a packet lost in flight leaves the destination's next
+        mailbox slot free."""
+        acts = [a for a in range(5) if (self.adv >> a) & 1]
+        order, fresh = (self.adv >> 8) & 3, (self.adv >> 12) & 1
+        if self._slots[0] != self._rnd:
+            self._slots = (self._rnd, {})
+        P0, v0, L0 = P, v, L
+        for dest in range(2, self.n + 1):
+            if dest == self.rank:
+                continue
+            go, action = 1, EV_HONEST
+            if self.dishonest:
+                if fresh:
+                    P, v, L = copy.copy(P0), v0, set(L0)
+                action = acts[self.rng.randint(len(acts))]
+                if action == ACT_MUTE:
+                    go = self.rng.randint(2)
+                elif action == ACT_REORDER:
+                    if order == ORDER_LOW:
+                        v = 1 if int(v) == 0 else 0
+                    else:
+                        v = self.rng.randint(self.n + 1 if order == ORDER_REFERENCE else self.w)
+                elif action == ACT_CLEAR_P:
+                    P.clear()
+                elif action == ACT_CLEAR_L:
+                    L.clear()
+            slot = EV_SLOT_MUTED
+            if go:
+                self.send(dest, P, v, L)
+                if self._lost:
+                    slot = EV_SLOT_LOST
+                else:
+                    k = self._slots[1].get(dest, 0)
+                    self._slots[1][dest] = k + 1
+                    slot = k if k < self.w else EV_SLOT_FULL
+            self._put(EV_SEND, dest, slot, action, len(L), packet_word(P, v, L))
+
+
+def trace_net_host(n: int, sizeL: int, n_dishonest: int, indices, seed_base: int, engine, lists=None,
+                   flip_q16: int = 0, adversary: Optional[int] = None, net: Optional[int] = None):
+    """The specification of the ``_net`` trace calls: :func:`trace_host` with
+    :class:`TraceNetParty` on the network ``net``, the same ``(rows, counts,
+    events)`` layout.  With ``net`` None or 0 it is :func:`trace_host` itself."""
+    lossy = 0 if net is None else check_net(net)
+    if not lossy:
+        return trace_host(n, sizeL, n_dishonest, indices, seed_base, engine, lists=lists, flip_q16=flip_q16,
+                          adversary=adversary)
+    word = check_adversary(ADV_REFERENCE if adversary is None else adversary)
+    indices = [int(i) for i in indices]
+    rows = np.zeros((len(indices), out_words(n)), np.int32)
+    counts = np.zeros((len(indices), n + 1), np.int32)
+    events = []
+    for j, i in enumerate(indices):
+        sink: Dict[int, TraceNetParty] = {}
+        cls = type("TraceNetParty_sink", (TraceNetParty,), {"sink": sink})
+        rows[j] = run_host(n, sizeL, n_dishonest, 1, (int(seed_base) + i) & MASK64, engine,
+                           lists=None if lists is None else np.asarray(lists)[j:j + 1], party_cls=cls,
+                           flip_q16=flip_q16, adversary=word, net=lossy)[0]
+        per_rank = [[] for _ in range(n + 1)]
+        if rows[j, 3] == 0:
+            for r in range(1, n + 1):
+                dec, vi = int(rows[j, 4 + 5 * r]), int(rows[j, 5 + 5 * r])
+                per_rank[r] = sink[r].events + [(event_head(EV_DECIDE, length=bin(vi).count("1")), dec & _U32)]
+        counts[j] = [len(e) for e in per_rank]
+        events.append(per_rank)
+    return rows, counts, events
+
+
+def replay(n: int, sizeL: int, n_dishonest: int, indices, seed: int, engine, flip_q16: int = 0,
+           adversary: Optional[int] = None, net: Optional[int] = None, cap: int = 1024) -> dict:
+    """The transcripts of the runs ``indices`` of a ``run`` / ``curve`` / ``grid``
+    item under ``seed`` (key = seed + index, the rule of ``failed_runs``), as the
+    device re-runs them: one trace call -- ``montecarlo_trace_sampled_net`` when
+    ``net`` is a non-zero network word, ``montecarlo_trace_sampled`` otherwise
+    -- and one synchronisation.  ``indices``: host integers or an int64 device
+    tensor (a tally's capture row).  Returns ``{"indices", "rows", "counts",
+    "events"}`` as host arrays, slot j belonging to ``indices[j]``;
+    :func:`format_trace` renders a slot.  A coalition's runs have no transcript:
+    there is no argument for its word."""
+    lossy = 0 if net is None else check_net(net)
+    if lossy:
+        out = engine.montecarlo_trace_sampled_net(n, n_dishonest, seed, indices, sizeL, cap=cap, flip_q16=flip_q16,
+                                                  adversary=adversary, net=lossy)
+    else:
+        out = engine.montecarlo_trace_sampled(n, n_dishonest, seed, indices, sizeL, cap=cap, flip_q16=flip_q16,
+                                              adversary=adversary)
+    if hasattr(indices, "cpu"):  # the indices come to the host with the outputs, as int32 pairs
+        import torch
+        rows, counts, events, pairs = _to_host(out + (indices.view(torch.int32),))
+        idx = [int(i) for i in np.ascontiguousarray(pairs).view(np.int64)]
+    else:
+        idx = [int(i) for i in indices]
+        rows, counts, events = _to_host(out)
+    return {"indices": idx, "rows": rows, "counts": counts, "events": events}
+
+
+def _to_host(tensors) -> tuple:
+    """Int32 device tensors as host arrays through one copy (one synchronisation)."""
+    import torch
+    flat = torch.cat([t.reshape(-1) for t in tensors]).cpu().numpy()
+    out, at = [], 0
+    for t in tensors:
+        out.append(flat[at:at + t.numel()].reshape(tuple(t.shape)))
+        at += t.numel()
+    return tuple(out)
+
+
 def trace_events(counts, events, j: int = 0) -> list:
     """Slot ``j`` of a device trace (int32 or uint32 arrays of
     ``Engine.montecarlo_trace_*``, on the host) as :func:`trace_host` lays its
@@ -1529,14 +1698,15 @@ def format_trace(n: int, row, counts, events) -> str:
         for head, pkt in events[r]:
             f = event_fields(head)
             if f["kind"] == EV_RECV:
-                what = f"accepted {_packet_text(pkt, f['len'])}" if f["code"] == 0 else \
+                what = "no packet arrived" if f["code"] == EV_NO_PACKET else \
+                    f"accepted {_packet_text(pkt, f['len'])}" if f["code"] == 0 else \
                     f"rejected, {VERDICTS[f['code']]}" if f["code"] <= 3 else \
                     f"consistent, not taken ({VERDICTS[f['code']]}: {_packet_text(pkt, f['len'])})"
                 out.append(f"[{name(r)} <- {name(f['peer'])}] round {f['round']}: {what}")
             elif f["kind"] == EV_SEND:
                 act = "" if f["code"] == EV_HONEST else f" (action: {ACTIONS[f['code']]})"
-                what = "does not send" if f["slot"] == EV_SLOT_MUTED else \
-                    f"{'drops (mailbox full)' if f['slot'] == EV_SLOT_FULL else 'sends'} {_packet_text(pkt, f['len'])}"
+                verb = {EV_SLOT_FULL: "drops (mailbox full)", EV_SLOT_LOST: "loses in flight"}.get(f["slot"], "sends")
+                what = "does not send" if f["slot"] == EV_SLOT_MUTED else f"{verb} {_packet_text(pkt, f['len'])}"
                 out.append(f"[{name(r)} -> {f['peer']}] round {f['round']}: {what}{act}")
             else:
                 dec = pkt - (1 << 32) if pkt >> 31 else pkt

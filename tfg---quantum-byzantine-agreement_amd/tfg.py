@@ -148,14 +148,37 @@ def _args(argv):
                          "the perfect network), e.g. 2@0,2@0x0100,2@0x1000:cmd,2:reorder_low@0x0400; one summary "
                          "line per sizeL and item; implies --fused; not with --sweep, --drop, --adversary, "
                          "--collude, --explain or --tables")
+    ap.add_argument("--replay", default=None, metavar="I[,J,...]",
+                    help="with --seed: re-run the runs I, J, ... of a --runs command with these flags (--flip, "
+                         "--adversary, --drop K[:cmd], --curve) on the device under key seed + index, the indices "
+                         "--failures prints, and print each one's transcript (montecarlo.replay, "
+                         "montecarlo.format_trace) headed 'run I', with --curve 'sizeL=C run I'; a lost packet shows "
+                         "as 'loses in flight', a lost commander packet as 'no packet arrived'; not with --runs, "
+                         "--collude, --sweep, --grid, --tables or --explain")
     ap.add_argument("--quiet", action="store_true", help="print only the outcome")
     ap.add_argument("--timing", action="store_true", help="print the wall time of the run")
     ap.add_argument("--wire", action="store_true",
                     help="in-process exact mode: send the lists in the reference's int64-per-bit wire layout "
                          "(tfg.py:142-161) instead of handing each rank its device row")
     a = ap.parse_args(argv)
+    if a.replay is not None:
+        given = [flag for flag, on in (("--runs", a.runs is not None), ("--collude", a.collude is not None),
+                                       ("--sweep", a.sweep is not None), ("--grid", a.grid is not None),
+                                       ("--tables", a.tables), ("--explain", a.explain)) if on]
+        if given:
+            ap.error(f"--replay: not with {', '.join(given)} (it re-runs the indices it is given, one transcript "
+                     "each; name a --grid or --sweep item's K, --adversary and --drop; a coalition's runs have no "
+                     "transcript)")
+        if a.seed is None:
+            ap.error("--replay needs --seed (key = seed + index)")
+        try:
+            a.replay = [int(x, 0) for x in a.replay.split(",") if x.strip()]
+        except ValueError:
+            ap.error("--replay: I[,J,...] are run indices (decimal or 0x hex)")
+        if not a.replay or min(a.replay) < 0 or max(a.replay) >= 1 << 64:
+            ap.error("--replay: at least one index, each in [0, 2^64)")
     if a.curve is not None:
-        if a.runs is None:
+        if a.runs is None and a.replay is None:
             ap.error("--curve needs --runs")
         a.curve = sorted(set(a.curve) | {int(a.sizeL)})
         if len(a.curve) > CURVE_MAX:
@@ -178,13 +201,13 @@ def _args(argv):
         if a.curve is not None or a.fused:
             ap.error("--tables: not with --curve or --fused")
     if a.flip is not None:
-        if a.runs is None:
+        if a.runs is None and a.replay is None:
             ap.error("--flip needs --runs")
         if not 0 <= a.flip <= 65535:
             ap.error("--flip: K must be in [0, 65535] (out of 65536)")
         a.fused = not a.tables
     if a.adversary is not None:
-        if a.runs is None:
+        if a.runs is None and a.replay is None:
             ap.error("--adversary needs --runs")
         from . import montecarlo
         try:
@@ -204,7 +227,7 @@ def _args(argv):
             ap.error(f"--collude: {e}")
         a.fused = True
     if a.drop is not None:
-        if a.runs is None:
+        if a.runs is None and a.replay is None:
             ap.error("--drop needs --runs")
         if a.collude is not None or a.sweep is not None or a.explain or a.tables:
             ap.error("--drop: not with --collude, --sweep, --explain or --tables (the coalition, sweep, trace and "
@@ -412,6 +435,20 @@ def _montecarlo(a, eng, size_l) -> int:
     return 0
 
 
+def _replay(a, eng, size_l) -> int:
+    """--replay I,J,...: the transcripts of those runs of the --runs command
+    with the same flags (montecarlo.replay), one per index, with --curve one
+    per sizeL and index."""
+    from . import montecarlo
+    for c in a.curve if a.curve is not None else [size_l]:
+        got = montecarlo.replay(a.parties, c, a.nDishonest, a.replay, a.seed, eng, flip_q16=a.flip or 0,
+                                adversary=a.adversary, net=a.drop, cap=EXPLAIN_CAP)
+        for i, row, counts, events in zip(got["indices"], got["rows"], got["counts"], got["events"]):
+            print(f"sizeL={c} run {i}" if a.curve is not None else f"run {i}")
+            print(montecarlo.format_trace(a.parties, row, counts, events))
+    return 0
+
+
 def main(argv=None) -> int:
     a = _args(sys.argv[1:] if argv is None else argv)
     size_l = int(a.sizeL)
@@ -424,6 +461,8 @@ def main(argv=None) -> int:
         return _torchrun(a, size_l, verbose, log)
     from .engine import Engine
     eng = Engine(0)
+    if a.replay is not None:
+        return _replay(a, eng, size_l)
     if a.runs is not None:
         return _montecarlo(a, eng, size_l)
     seed = secrets.randbits(20) if a.seed is None else a.seed

@@ -87,6 +87,12 @@ instances x n = 7 x sizeL = 1e5, 2 dishonest, on one GPU.
       the yardstick: the trace is that call plus the event stores -- with the
       rows of the two compared, and the host wall time of montecarlo.trace_host
       for 16 runs on the engine's own count tables.
+      With --drop K[:cmd] (repeatable): the montecarlo_trace_sampled_net call
+      at net = 0 and at each network word, at 16 and at --instances indices,
+      beside two calls whose code the build leaves as it was, timed in the same
+      session: montecarlo_curve_sampled_net at one checkpoint over as many
+      instances under the same word (rows compared), and
+      montecarlo_trace_sampled at net = 0 (rows, counts and events compared).
 
 (a), (b), (d), the --tally calls, the --flip calls and the --curve pair are device-event times of single calls on warm code: median, min
 and max over --repeats launches after --warmup launches.  (c) is host wall
@@ -164,14 +170,16 @@ def main(argv=None) -> int:
     ap.add_argument("--trace", action="store_true",
                     help="time montecarlo_trace_sampled at 16 and at --instances indices beside montecarlo_sampled "
                          "with the reference policy word at the same shapes, and the host wall time of trace_host "
-                         "for 16 runs, at each --sizeL; nothing else is measured")
+                         "for 16 runs, at each --sizeL; with --drop: montecarlo_trace_sampled_net at net = 0 and at "
+                         "each network word beside montecarlo_curve_sampled_net and montecarlo_trace_sampled; "
+                         "nothing else is measured")
     a = ap.parse_args(argv)
     if a.trace and (a.sweep or a.adversary or a.flip or a.curve or a.tally or a.tables):
         ap.error("--trace goes with --sizeL alone")
     if a.collude and (a.trace or a.sweep or a.flip or a.curve or a.tally or a.tables):
         ap.error("--collude goes with --sizeL and --adversary alone")
-    if a.drop and (a.collude or a.trace or a.sweep or a.flip or a.curve or a.tally or a.tables):
-        ap.error("--drop goes with --sizeL and --adversary alone")
+    if a.drop and (a.collude or a.sweep or a.flip or a.curve or a.tally or a.tables):
+        ap.error("--drop goes with --sizeL and --adversary (or --trace) alone")
     if a.grid and (a.sweep or a.drop or a.collude or a.trace or a.flip or a.tally or a.tables or a.adversary):
         ap.error("--grid goes with --sizeL or --curve alone")
     if a.sweep and (a.flip or a.tally or a.tables or a.adversary):
@@ -185,6 +193,8 @@ def main(argv=None) -> int:
     if a.grid:
         shapes = [[s] for s in (a.sizeL or [])] + [sorted({int(c) for c in text.split(",")}) for text in a.curve or []]
         lines = [json.dumps(_measure_grid(a, eng, counts, text)) for text in a.grid for counts in shapes or [[100_000]]]
+    elif a.trace and a.drop:
+        lines = [json.dumps(_measure_nettrace(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
     elif a.drop:
         lines = [json.dumps(_measure_drop(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
     elif a.collude:
@@ -516,6 +526,54 @@ def _measure_trace(a, eng, size_l) -> dict:
     res["trace_host_16_runs_wall_s"] = time.perf_counter() - t0
     dev = eng.montecarlo_trace_sampled(n, nd, a.seed, list(range(16)), size_l, cap=cap)
     res["trace_host_rows_equal_device"] = bool((dev[0].cpu().numpy() == host[0]).all())
+    return res
+
+
+def _measure_nettrace(a, eng, size_l) -> dict:
+    """--trace --drop: the lossy-network trace call at net = 0 and at each
+    network word, at 16 and at --instances indices, beside the lossy-network
+    decision call of one checkpoint under the same word and beside the trace
+    call on the perfect network."""
+    import torch
+    mc = importlib.import_module(f"{PKG}.montecarlo")
+    n, nd, cap = a.parties, a.dishonest, 256
+    res = {"config": {"n": n, "sizeL": size_l, "dishonest": nd, "seed": a.seed, "cap": cap, "adversary": "0xf",
+                      "device": torch.cuda.get_device_name(0)}, "indices": {}}
+    words = [0] + [w for w in (mc.parse_net(x) for x in a.drop) if w]
+    for k in sorted({16, a.instances}):
+        idx = torch.arange(k, dtype=torch.int64, device=eng.device)
+        ref = eng.montecarlo_trace_sampled(n, nd, a.seed, idx, size_l, cap=cap)
+        out = tuple(torch.zeros_like(t) for t in ref)
+        rows = eng.montecarlo_curve_sampled_net(n, nd, a.seed, k, [size_l], adversary=0xF)
+        r = {"trace": _events(lambda: eng.montecarlo_trace_sampled(n, nd, a.seed, idx, size_l, cap=cap, out=ref),
+                              a.warmup, a.repeats), "nets": {}}
+        for word in words:
+            t = {"nettrace": _events(lambda: eng.montecarlo_trace_sampled_net(n, nd, a.seed, idx, size_l, cap=cap,
+                                                                              out=out, net=word),
+                                     a.warmup, a.repeats),
+                 "decide_net": _events(lambda: eng.montecarlo_curve_sampled_net(n, nd, a.seed, k, [size_l], rows,
+                                                                                adversary=0xF, net=word),
+                                       a.warmup, a.repeats)}
+            t["rows_equal_decide_net"] = bool(torch.equal(out[0], rows[0]))
+            if not t["rows_equal_decide_net"]:
+                raise SystemExit(f"the traced rows are not the decision call's (n={n}, sizeL={size_l}, net={word:#x})")
+            if not word:
+                t["equal_trace_call"] = all(bool(torch.equal(x, y)) for x, y in zip(out, ref))
+                if not t["equal_trace_call"]:
+                    raise SystemExit(f"net = 0 does not give the trace call's outputs (n={n}, sizeL={size_l})")
+            t["successes"] = int(out[0][:, 0].sum())
+            t["events_per_instance"] = float(out[1].sum().item()) / k
+            t["events_past_cap"] = int((out[1] > cap).sum().item())
+            t["nettrace_over_decide_net_at_median"] = t["nettrace"]["median_ms"] / t["decide_net"]["median_ms"]
+            t["nettrace_over_trace_at_median"] = t["nettrace"]["median_ms"] / r["trace"]["median_ms"]
+            for other in ("decide_net", "trace") if not word else ("decide_net",):
+                o = t[other] if other == "decide_net" else r["trace"]
+                t[f"ranges_overlap_{other}"] = not (t["nettrace"]["min_ms"] > o["max_ms"] or
+                                                    t["nettrace"]["max_ms"] < o["min_ms"])
+            r["nets"][f"{word:#x}"] = t
+        r["trace_again"] = _events(lambda: eng.montecarlo_trace_sampled(n, nd, a.seed, idx, size_l, cap=cap, out=ref),
+                                   a.warmup, a.repeats)
+        res["indices"][str(k)] = r
     return res
 
 
