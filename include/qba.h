@@ -874,6 +874,62 @@ QBA_API int qba_montecarlo_grid_lists(qba_ctx *ctx, int n_parties, uint64_t seed
                                       const qba_mc_grid_scenario *scen_host, int n_scen, const uint8_t *lists_dev,
                                       uint64_t ld, uint64_t inst_stride, int32_t *out_dev, qba_stream stream);
 
+/* ---- noise profiles ------------------------------------- */
+/* The two _adv curve calls with a noise profile in place of flip_q16: a flip
+ * rate per list row and depolarised entries.
+ *   rates_host[g], g = 0 .. n_parties   every measured bit of list row g flips
+ *                          with probability rates_host[g] / 65536 (row 0: the
+ *                          commander's list, row 1: Lc, row g >= 2: lieutenant g)
+ *   depol_q16              with probability depol_q16 / 65536 the whole entry
+ *                          is depolarised: a uniform value below w is XORed
+ *                          into every row's value at once
+ * Entry e of the instance keyed key = seed_base + i gets 64 bits r; row g's
+ * value is XORed with (r >> 4g) & (w - 1), where the flip_q16 calls XOR theirs.
+ * With word(t) = output word t % 4 of philox4x32-10(ctr = {e_lo, e_hi, t / 4,
+ * 0x4E4F4953}, key = {key_lo, key_hi}), the noise stream of the flip_q16 calls:
+ *   r = 0
+ *   if any rate is not 0:
+ *     j0 = the lowest set bit of any rate
+ *     for s = 0 .. 15 - j0:
+ *       x = word(2s) | word(2s+1) << 32
+ *       M_s = nibble g is 0xF where bit (j0 + s) of rates_host[g] is set, else 0
+ *       r = ((r | x) & M_s) | ((r & x) & ~M_s)
+ *   if depol_q16 != 0:
+ *     d = philox4x32-10(ctr = {e_lo, e_hi, 8, 0x4E4F4953}, key)
+ *     if (d[0] & 0xFFFF) < depol_q16:  r ^= d[2] | d[3] << 32
+ * Every bit of row g's mask is 1 with probability exactly rates_host[g] /
+ * 65536 and a row with rate 0 keeps its values.  With every rate equal to k
+ * and depol_q16 == 0 the rows are those of the _adv curve call at flip_q16 = k
+ * word for word; the all-zero profile draws nothing and gives that call's rows
+ * at flip_q16 = 0.  Noise never raises status bit 2.
+ *
+ * Checked right after `adv` and before ctx, each QBA_EINVAL naming the field:
+ * n_rates == n_parties + 1, rates_host not NULL, depol_q16 <= 65535.  The out
+ * layout, status bits, every other check and its order, asynchrony and capture
+ * legality are those of the _adv curve calls; the profile travels by value in
+ * the kernel arguments, rates_host may be reused when the call returns, and the
+ * calls allocate and copy nothing; a single sizeL is a curve of one checkpoint;
+ * qba_montecarlo_tally takes the rows as they are.  The kernels hold no LDS
+ * beyond the _adv curve kernels': qba_montecarlo_curve_shape is their launch
+ * shape.  Specification: montecarlo.noise_masks_profile. */
+QBA_API int qba_montecarlo_curve_sampled_nprof(qba_ctx *ctx, int n_parties, int n_dishonest, uint64_t seed_base,
+                                               int64_t n_instances, const uint32_t *counts_host, int n_counts,
+                                               int32_t *out_dev, qba_stream stream, uint32_t adv,
+                                               const uint16_t *rates_host, int n_rates, uint32_t depol_q16);
+QBA_API int qba_montecarlo_curve_lists_nprof(qba_ctx *ctx, int n_parties, int n_dishonest, uint64_t seed_base,
+                                             int64_t n_instances, const uint32_t *counts_host, int n_counts,
+                                             const uint8_t *lists_dev, uint64_t ld, uint64_t inst_stride,
+                                             int32_t *out_dev, qba_stream stream, uint32_t adv,
+                                             const uint16_t *rates_host, int n_rates, uint32_t depol_q16);
+/* The masks of a profile XORed in place into lists in the layout of
+ * qba_sample_check_batched (qba_noise_apply_batched with a profile): the
+ * profile is checked first, as above, then that call's arguments as it checks
+ * them.  Asynchronous, allocates and copies nothing, legal in a stream
+ * capture; needs no program. */
+QBA_API int qba_noise_profile_apply(qba_ctx *ctx, int n_parties, uint64_t seed_base, int64_t n_instances,
+                                    uint64_t count, const uint16_t *rates_host, int n_rates, uint32_t depol_q16,
+                                    uint8_t *lists_dev, uint64_t ld, uint64_t inst_stride, qba_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,12 @@ SIGNATURES = {
     "qba_montecarlo_grid_lists": [_p, C.c_int, _u64, _i64, C.POINTER(C.c_uint32), C.c_int, C.POINTER(GridScenario),
                                   C.c_int, _p, _u64, _u64, _p, _p],
     "qba_noise_apply_batched": [_p, C.c_int, _u64, _i64, _u64, C.c_uint32, _p, _u64, _u64, _p],
+    "qba_montecarlo_curve_sampled_nprof": [_p, C.c_int, C.c_int, _u64, _i64, C.POINTER(C.c_uint32), C.c_int, _p, _p,
+                                           C.c_uint32, C.POINTER(C.c_uint16), C.c_int, C.c_uint32],
+    "qba_montecarlo_curve_lists_nprof": [_p, C.c_int, C.c_int, _u64, _i64, C.POINTER(C.c_uint32), C.c_int, _p, _u64,
+                                         _u64, _p, _p, C.c_uint32, C.POINTER(C.c_uint16), C.c_int, C.c_uint32],
+    "qba_noise_profile_apply": [_p, C.c_int, _u64, _i64, _u64, C.POINTER(C.c_uint16), C.c_int, C.c_uint32, _p, _u64,
+                                _u64, _p],
     "qba_montecarlo_curve_shape": [C.c_int, C.POINTER(C.c_int), _pi64, C.POINTER(C.c_int)],
     "qba_montecarlo_program_shape": [_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                      C.POINTER(C.c_int), _pi64, C.POINTER(C.c_int)],

@@ -92,6 +92,11 @@ int qba_launch_mc_net(qba_ctx *ctx, const QbaMc &M);
 // the curve under every scenario of M.grid, through the grid kernel (qba_mc_grid_inst.hip)
 template <int NP>
 int qba_launch_mc_grid(qba_ctx *ctx, const QbaMc &M);
+// the curve under a policy and a noise profile (qba_noise_profile.h), through the noise-profile kernel
+// (qba_mc_nprof_inst.hip); M.noise is not read
+struct QbaNoiseProfile;
+template <int NP>
+int qba_launch_mc_nprof(qba_ctx *ctx, const QbaMc &M, const QbaNoiseProfile &P);
 // qba_montecarlo_shape, or (curve) qba_montecarlo_curve_shape
 template <int NP>
 void qba_mc_shape_n(int curve, int *waves, int64_t *lds, int *wgs);

@@ -6,6 +6,7 @@
 #include "qba_proto_adv.h"
 #include "qba_proto_coal.h"
 #include "qba_proto_net.h"
+#include "qba_noise_profile.h"
 
 // Experiment builds only (tools/exp): restrict instantiation to one n.
 #ifndef QBA_ONLY_N
@@ -235,6 +236,27 @@ extern "C" int qba_montecarlo_curve_sampled_net(qba_ctx *ctx, int n, int n_dis, 
   return with_n(n, [&](auto k) { return qba_launch_mc_net<decltype(k)::value>(ctx, M); });
 }
 
+// The curve call under a noise profile: the _adv
+// curve call's arguments without flip_q16, then the profile, checked right
+// after the policy word and before ctx.  The profile travels in the kernel
+// arguments: nothing is allocated or copied.
+extern "C" int qba_montecarlo_curve_sampled_nprof(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
+                                                  const uint32_t *counts, int n_counts, int32_t *out,
+                                                  qba_stream stream, uint32_t adv, const uint16_t *rates,
+                                                  int n_rates, uint32_t depol_q16) {
+  const char *who = "qba_montecarlo_curve_sampled_nprof";
+  QbaMc M{who, nullptr, seed_base, n_inst, n_dis, out, (hipStream_t)stream, {}, 1, {}, adv, 1};
+  const char *bad = qba_adv_bad(adv);
+  if (!bad) bad = qba_nprof_bad(n, rates, n_rates, depol_q16);
+  if (int rc = qba_mc_curve_check(who, ctx, n, n_dis, n_inst, counts, n_counts, out, &M.counts, bad)) return rc;
+  const QbaNoiseProfile P = qba_nprof_of(rates, n_rates, depol_q16);
+  if (int rc = need_program(ctx, n, who)) return rc;
+  if (n_inst == 0) return QBA_OK;
+  if (int rc = qba_set_device(ctx)) return rc;
+  M.ps = (const QbaProgramSet *)ctx->prog_dev[n];
+  return with_n(n, [&](auto k) { return qba_launch_mc_nprof<decltype(k)::value>(ctx, M, P); });
+}
+
 // The curve call under every scenario of a list: one
 // pass over the entries, the rounds once per checkpoint and scenario.  Checked
 // in the order counts, flip_q16, scenarios, ctx (qba_mc_sweep_check).
@@ -289,6 +311,26 @@ extern "C" int qba_noise_apply_batched(qba_ctx *ctx, int n, uint64_t seed_base, 
                                 "multiple of 4; count < 2^31)");
   if (n_inst == 0 || count == 0 || flip_q16 == 0) return QBA_OK;
   return qba_launch_noise_apply(n, seed_base, n_inst, count, flip_q16, lists, ld, inst_stride, (hipStream_t)stream);
+}
+
+// The masks of a noise profile into lists in that layout, in place
+// (qba_proto_nprof.hip): the profile's checks first,
+// as the profile curve calls make them, then qba_noise_apply_batched's.
+extern "C" int qba_noise_profile_apply(qba_ctx *ctx, int n, uint64_t seed_base, int64_t n_inst, uint64_t count,
+                                       const uint16_t *rates, int n_rates, uint32_t depol_q16, uint8_t *lists,
+                                       uint64_t ld, uint64_t inst_stride, qba_stream stream) {
+  const char *who = "qba_noise_profile_apply";
+  if (n >= 1 && n <= QBA_MAX_PARTIES)  // n_parties itself is check_common's refusal
+    if (const char *bad = qba_nprof_bad(n, rates, n_rates, depol_q16))
+      return qba_fail(QBA_EINVAL, std::string(who) + ": " + bad);
+  if (int rc = check_common(ctx, n, lists, count, ld, who)) return rc;
+  if (n_inst < 0 || (n_inst > 1 && inst_stride < (uint64_t)(n + 1) * ld) || (inst_stride & 3) ||
+      count >= (1ull << 31))
+    return qba_fail(QBA_EINVAL, std::string(who) + ": bad arguments (inst_stride >= (n+1)*ld, "
+                                "multiple of 4; count < 2^31)");
+  const QbaNoiseProfile P = qba_nprof_of(rates, n_rates, depol_q16);
+  if (n_inst == 0 || count == 0 || !(P.steps | P.depol)) return QBA_OK;
+  return qba_launch_nprof_apply(n, seed_base, n_inst, count, P, lists, ld, inst_stride, (hipStream_t)stream);
 }
 
 static int mc_shape(const char *who, int n, int curve, int *waves, int64_t *lds_bytes, int *wgs_per_cu) {

@@ -1023,6 +1023,93 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64, NW * 64)))
 }
 #endif
 
+// ---------------------------------------------------------------------------
+// qba_k_nprof_sampled: qba_k_mc_curve_sampled_adv with the masks of a noise
+// profile (qba_nprof_r, qba_noise_profile.h) where
+// that kernel XORs the flips of section 13.5: a rate per list row and
+// depolarised entries instead of the one flip_q16.  The profile is a kernel
+// argument (its ladder masks are read as wave-uniform scalars) and takes no
+// LDS: the launch shape is the curve kernels'.  The rounds are
+// proto_rounds_adv.  Only the curve form exists; a single count is a curve of
+// one checkpoint.  A text of its own, seen by qba_mc_nprof_inst.hip alone.
+// ---------------------------------------------------------------------------
+#if defined(QBA_MC_NPROF_INST)
+#include "qba_noise_profile.h"
+template <int NP, int SAMP, int NW>
+__global__ void __attribute__((amdgpu_flat_work_group_size(64, NW * 64)))
+    qba_k_nprof_sampled(const QbaProgramSet *__restrict__ ps, uint64_t seed_base, int64_t n_inst, int n_dis,
+                        int nw_run, int32_t *__restrict__ out, const QbaMcCounts cv, uint32_t adv,
+                        const QbaNoiseProfile np) {
+  using C = QCfg<NP>;
+  constexpr int ND = CF<NP>::ND;
+  constexpr size_t WAVE_WORDS = (qba_mc_wave_lds(C::G, C::W) + qba_mc_acc_lds(C::G, C::W)) / sizeof(uint32_t);
+  extern __shared__ __align__(16) uint64_t lds[];
+  const uint64_t *pat, *apat, *thr;
+  const uint32_t *pl;
+  uint32_t *waves = qba_stage<NP, 1, SAMP, NW * 64>(ps, lds, pat, apat, thr, pl);
+  __syncthreads();
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = (int)__lane_id();
+  if (wv >= nw_run) return;
+  uint32_t *mine = waves + (size_t)wv * WAVE_WORDS;
+  ProtoShared &S = *reinterpret_cast<ProtoShared *>(mine);
+  uint32_t *box = mine + PROTO_S_WORDS;
+  uint32_t *acc = mine + qba_mc_wave_lds(C::G, C::W) / sizeof(uint32_t);
+  uint32_t *mcw = acc + C::W * C::G;  // the AND words and the flags, as mc_entry addresses them
+  const bool noisy = (np.steps | np.depol) != 0u;
+  const int64_t stride = (int64_t)gridDim.x * nw_run;
+  for (int64_t inst = (int64_t)blockIdx.x * nw_run + wv; inst < n_inst; inst += stride) {
+    const uint64_t key = seed_base + (uint64_t)inst;
+    const uint32_t k0 = __builtin_amdgcn_readfirstlane((uint32_t)key);
+    const uint32_t k1 = __builtin_amdgcn_readfirstlane((uint32_t)(key >> 32));
+    mc_acc_begin(acc, C::G, C::W, lane);  // nothing but the segments touches the area
+    uint32_t seen = 0, bad = 0, lo = 0;
+    for (int j = 0; j < cv.n; ++j) {
+      const uint32_t hi = cv.c[j];
+      proto_sync<false>();  // the area is set up; the previous row's stores have read S
+      if constexpr (SAMP == QBA_S_CLOSED) {
+        // pairs [lo / 2, ceil(hi / 2)), lane l the l-th, l + 64-th, ... of them;
+        // a checkpoint at an odd count splits a pair, whose block is then drawn
+        // in both segments and gives each its half
+        const uint32_t pend = (hi + 1u) >> 1;
+        for (uint32_t p = (lo >> 1) + (uint32_t)lane; p < pend; p += 64u) {
+          const QbaU4 x = qba_philox(p, 0u, 0u, 0u, k0, k1);
+#pragma unroll
+          for (uint32_t h = 0; h < 2; ++h) {
+            const uint32_t e = 2u * p + h;
+            if (e < lo || e >= hi) continue;
+            uint32_t d[ND], D[4] = {0u, 0u, 0u, 0u};
+            qba_closed_half<NP>(h ? x.z : x.x, h ? x.w : x.y, (uint64_t)p, h, k0, k1, pl, d);
+#pragma unroll
+            for (int i = 0; i < ND; ++i) D[i] = d[i];
+            if (noisy) qba_noise_d<C::G, C::W>(qba_nprof_r(e, 0u, k0, k1, np), D);
+            mc_entry_at<false>(acc, C::G, mcw, D, C::G, C::W, seen, bad);
+          }
+        }
+      } else {
+        for (uint32_t e = lo + (uint32_t)lane; e < hi; e += 64u) {
+          uint32_t d[ND], D[4] = {0u, 0u, 0u, 0u};
+          qba_entry_d<NP, SAMP>((uint64_t)e, k0, k1, ps, pat, apat, thr, pl, d);
+#pragma unroll
+          for (int i = 0; i < ND; ++i) D[i] = d[i];
+          if (noisy) qba_noise_d<C::G, C::W>(qba_nprof_r(e, 0u, k0, k1, np), D);
+          mc_entry_at<false>(acc, C::G, mcw, D, C::G, C::W, seen, bad);
+        }
+      }
+      mc_flags(mcw, C::G, C::W, seen, bad);
+      proto_sync<false>();
+      uint32_t st;
+      const uint32_t pnz = mc_acc_finish<false>(S, acc, C::G, C::W, lane, st);
+      proto_sync<false>();
+      proto_rounds_adv<false>(S, box, NP, n_dis, key, pnz, st, lane,
+                              out + ((int64_t)j * n_inst + inst) * (int64_t)(4 + 5 * C::G), adv);
+      lo = hi;
+    }
+    proto_sync<false>();  // the last finish has read the area
+  }
+}
+#endif
+
 // The sampled kernel of (NP, SAMP) for one count (qba_k_mc_sampled) or for a
 // curve (qba_k_mc_curve_sampled), or (NOISE) the noisy form of either, as the
 // host sees it; everything below is written once over this.  The noisy kernels
@@ -1123,7 +1210,8 @@ static int qba_mc_with_kern(qba_ctx *ctx, bool curve, const F &f) {
 // sweep kernel by qba_mc_sweep_inst.hip, the trace kernel by qba_mc_trace_inst.hip,
 // the coalition kernel by qba_mc_coal_inst.hip, the lossy-network kernel by
 // qba_mc_net_inst.hip, the grid kernel by qba_mc_grid_inst.hip, the
-// lossy-network trace kernel by qba_mc_nettrace_inst.hip.
+// lossy-network trace kernel by qba_mc_nettrace_inst.hip, the noise-profile
+// kernel by qba_mc_nprof_inst.hip.
 #if defined(QBA_MC_TRACE_INST)
 // The trace kernel of (NP, SAMP): the single-count _adv kernels' description
 // (wave count, run_shape) with its own kernel and argument list.
@@ -1290,6 +1378,31 @@ int qba_launch_mc_nettrace(qba_ctx *ctx, const QbaNetTrace &N) {
     const void *args[] = {&T.ps,   &T.seed_base, &T.idx,    &T.n_idx,  &T.n_match, &T.count, &T.n_dis, &nw_run,
                           &T.rows, &T.counts,    &T.events, &T.noise,  &T.adv,     &T.cap,   &N.net};
     QBA_HIP(hipLaunchKernel(K::kernel(), dim3(grid), dim3(K::NW * 64), const_cast<void **>(args), sh.lds, T.stream));
+    QBA_HIP(hipGetLastError());
+    return QBA_OK;
+  });
+}
+#elif defined(QBA_MC_NPROF_INST)
+// The noise-profile kernel of (NP, SAMP): the curve _adv kernels' description
+// (wave count, EXTRA, run_shape) with its own kernel and argument list.
+template <int NP, int SAMP>
+struct QbaMcNprofKern : QbaMcKern<NP, SAMP, true, false, true> {
+  using Base = QbaMcKern<NP, SAMP, true, false, true>;
+  static const void *kernel() { return (const void *)qba_k_nprof_sampled<NP, SAMP, Base::NW>; }
+};
+template <int NP>
+int qba_launch_mc_nprof(qba_ctx *ctx, const QbaMc &M, const QbaNoiseProfile &P) {
+  return qba_mc_with_program<NP>(ctx, [&](auto s, size_t tables) -> int {
+    using K = QbaMcNprofKern<NP, decltype(s)::value>;
+    const QbaMcShape sh = K::run_shape(tables);
+    if (sh.waves < 1)
+      return qba_fail(QBA_EUNSUPPORTED, std::string(M.who) + ": the program's tables leave no LDS for a wave");
+    if (int rc = lds_allow(K::kernel(), sh.lds)) return rc;
+    const int64_t need = (M.n_inst + sh.waves - 1) / sh.waves, cap = (int64_t)ctx->num_cus * sh.wgs;
+    const int grid = (int)(need < cap ? need : cap);
+    const int nw_run = sh.waves;
+    const void *args[] = {&M.ps, &M.seed_base, &M.n_inst, &M.n_dis, &nw_run, &M.out, &M.counts, &M.adv, &P};
+    QBA_HIP(hipLaunchKernel(K::kernel(), dim3(grid), dim3(K::NW * 64), const_cast<void **>(args), sh.lds, M.stream));
     QBA_HIP(hipGetLastError());
     return QBA_OK;
   });

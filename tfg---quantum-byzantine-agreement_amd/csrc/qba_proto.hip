@@ -19,6 +19,7 @@
 #include "qba_proto_adv.h"  // the entry points' policy check and launches; the kernels here keep qba_proto_rounds.h
 #include "qba_proto_coal.h"  // ... and the coalition word's check and launch
 #include "qba_proto_net.h"   // ... and the network word's
+#include "qba_noise_profile.h"  // ... and the noise profile's
 
 namespace {
 
@@ -407,6 +408,31 @@ extern "C" int qba_montecarlo_curve_lists_net(qba_ctx *ctx, int n, int n_dis, ui
   return launch_chunks(ctx, n_inst, [&](int64_t first, dim3 grid) {
     qba_launch_mc_net_lists(grid, lds, (hipStream_t)stream, n, n_dis, seed_base, first, n_inst, lists, ld,
                             inst_stride, out, cv, adv, net);
+  });
+}
+
+// qba_montecarlo_curve_lists_adv under a noise profile (DESIGN.md section
+// 13.14): the kernel of qba_proto_nprof.hip, in that call's LDS layout, which
+// XORs the profile's masks into the rows it reads.  The profile is checked
+// right after the policy word.
+extern "C" int qba_montecarlo_curve_lists_nprof(qba_ctx *ctx, int n, int n_dis, uint64_t seed_base, int64_t n_inst,
+                                                const uint32_t *counts, int n_counts, const uint8_t *lists,
+                                                uint64_t ld, uint64_t inst_stride, int32_t *out, qba_stream stream,
+                                                uint32_t adv, const uint16_t *rates, int n_rates,
+                                                uint32_t depol_q16) {
+  const char *who = "qba_montecarlo_curve_lists_nprof";
+  QbaMcCounts cv;
+  const char *bad = qba_adv_bad(adv);
+  int rc = qba_mc_curve_check(who, ctx, n, n_dis, n_inst, counts, n_counts, out, &cv,
+                              bad ? bad : qba_nprof_bad(n, rates, n_rates, depol_q16));
+  if (rc || (rc = lists_check(who, n, n_inst, cv.c[cv.n - 1], lists, ld, inst_stride)) || n_inst == 0) return rc;
+  const QbaNoiseProfile P = qba_nprof_of(rates, n_rates, depol_q16);
+  const int G = n + 1, w = 1 << qba_nq(n);
+  const size_t lds = (size_t)(PROTO_S_WORDS + ((proto_box_words(G, w) + 3) & ~3) + mc_acc_words(G, w)) *
+                     sizeof(uint32_t);  // the _adv curve call's: <= 37024 B
+  return launch_chunks(ctx, n_inst, [&](int64_t first, dim3 grid) {
+    qba_launch_nprof_lists(grid, lds, (hipStream_t)stream, n, n_dis, seed_base, first, n_inst, lists, ld,
+                           inst_stride, out, cv, adv, P);
   });
 }
 

@@ -572,6 +572,67 @@ class Engine:
              (C.c_uint32 * len(cs))(*cs), len(cs), _ptr(lists), ld, stride, _ptr(out), self.stream(), adv, word)
         return out
 
+    # -- the curve under a noise profile (qba_montecarlo_curve_*_nprof) ------------
+    @staticmethod
+    def _check_noise(n: int, noise):
+        """A noise profile ``(rates, depol_q16)`` (None: all zero) checked on the
+        host, as the calls take it: ``(uint16 array, n + 1, depol_q16)``."""
+        from .montecarlo import check_noise_profile
+        rates, depol = check_noise_profile(n, *(((0,) * (n + 1), 0) if noise is None else noise))
+        return (C.c_uint16 * len(rates))(*rates), len(rates), depol
+
+    def montecarlo_curve_sampled_nprof(self, n: int, n_dishonest: int, seed_base: int, n_inst: int, counts,
+                                       out: Optional[torch.Tensor] = None, adversary: Optional[int] = None,
+                                       noise=None) -> torch.Tensor:
+        """montecarlo_curve_sampled under a noise profile
+        (qba_montecarlo_curve_sampled_nprof): the same rows layout, the
+        dishonest parties under the policy ``adversary`` (None: the reference's
+        0xF) and every entry XORed with the masks of ``noise`` = ``(rates,
+        depol_q16)`` (montecarlo.noise_masks_profile; None: the all-zero
+        profile, the rows of the ``adversary`` call without noise)."""
+        self._check_n(n)
+        cs = self._check_curve(n, n_dishonest, n_inst, counts)
+        adv = self._check_adversary(0xF if adversary is None else adversary)
+        rates, n_rates, depol = self._check_noise(n, noise)
+        self.prepare(n)
+        out = self._rows_out(n, n_inst, out, len(cs))
+        call("qba_montecarlo_curve_sampled_nprof", self.ctx, n, n_dishonest, _u64(seed_base), n_inst,
+             (C.c_uint32 * len(cs))(*cs), len(cs), _ptr(out), self.stream(), adv, rates, n_rates, depol)
+        return out
+
+    def montecarlo_curve_lists_nprof(self, n: int, n_dishonest: int, seed_base: int, lists, counts,
+                                     out: Optional[torch.Tensor] = None, adversary: Optional[int] = None,
+                                     noise=None) -> torch.Tensor:
+        """The same from injected lists (qba_montecarlo_curve_lists_nprof), as
+        montecarlo_curve_lists takes them: the masks are XORed into the rows as
+        the kernel reads them, ``lists`` stays as it is."""
+        self._check_n(n)
+        cs = self._check_curve(n, n_dishonest, 0, counts)
+        adv = self._check_adversary(0xF if adversary is None else adversary)
+        rates, n_rates, depol = self._check_noise(n, noise)
+        lists, n_inst, ld, stride = self._mc_lists(n, lists, cs[-1])
+        out = self._rows_out(n, n_inst, out, len(cs))
+        call("qba_montecarlo_curve_lists_nprof", self.ctx, n, n_dishonest, _u64(seed_base), n_inst,
+             (C.c_uint32 * len(cs))(*cs), len(cs), _ptr(lists), ld, stride, _ptr(out), self.stream(), adv, rates,
+             n_rates, depol)
+        return out
+
+    def noise_profile_apply(self, n: int, seed_base: int, lists: torch.Tensor, count: int, noise) -> torch.Tensor:
+        """XOR the masks of the profile ``noise`` = ``(rates, depol_q16)``
+        (montecarlo.noise_masks_profile under key seed_base + i) into columns
+        [0, count) of the uint8 [n_inst, n+1, ld] device lists of
+        sample_check_batched, in place (qba_noise_profile_apply); returns
+        ``lists``."""
+        self._check_n(n)
+        rates, n_rates, depol = self._check_noise(n, noise)
+        if not isinstance(lists, torch.Tensor) or lists.dtype != torch.uint8 or lists.dim() != 3 or \
+                lists.shape[1] != n + 1 or lists.device != self.device or lists.stride(2) != 1 or \
+                lists.shape[2] < count:
+            raise QbaError("lists must be a uint8 [n_inst, n+1, >= count] device tensor with unit column stride")
+        call("qba_noise_profile_apply", self.ctx, n, _u64(seed_base), lists.shape[0], count, rates, n_rates, depol,
+             _ptr(lists), lists.stride(1), lists.stride(0), self.stream())
+        return lists
+
     # -- a grid of scenarios per checkpoint in one pass (qba_montecarlo_sweep_*) ----
     SWEEP_MAX = 16  # QBA_MC_SWEEP_MAX
 

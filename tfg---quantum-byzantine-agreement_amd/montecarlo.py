@@ -73,6 +73,12 @@ A grid (:func:`grid`, ``Engine.montecarlo_grid_sampled`` /
 network word in every scenario, ``(n_dishonest, word, net)``: one pass, and
 along ``drop_q16`` the loss decisions are nested.  :func:`grid_host` is its
 specification.
+
+Noise profiles (``noise=(rates, depol_q16)`` on :func:`run`, :func:`curve` and
+their host forms): a flip rate per list row and a
+probability that a whole entry is depolarised, in place of the one
+``flip_q16``; built by :func:`noise_profile` or :func:`parse_noise_profile`.
+:func:`noise_masks_profile` is the definition; ``None`` is "no profile".
 """
 from __future__ import annotations
 
@@ -233,6 +239,165 @@ def noisy_lists(n: int, key: int, lists, flip_q16: int) -> np.ndarray:
     """``lists`` [n+1, count] with :func:`noise_masks` XORed in (a new uint8 array)."""
     L = np.array(lists, dtype=np.uint8).reshape(n + 1, -1)
     return L ^ noise_masks(n, key, L.shape[1], flip_q16)
+
+
+# ---------------------------------------------------------------------------
+# Noise profiles (DESIGN.md section 13.14)
+# ---------------------------------------------------------------------------
+DEPOL_CTR = 8  # word 2 of the depolarisation counter; the ladder's are 0..7
+
+
+def _q16(value, what: str) -> int:
+    """``value`` as an int in [0, 65535]; QbaError naming ``what`` otherwise
+    (bools and non-integers included)."""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise QbaError(f"noise profile: {what} must be an integer, not {value!r}")
+    if not 0 <= int(value) <= 65535:
+        raise QbaError(f"noise profile: {what}={int(value)} outside [0, 65535]")
+    return int(value)
+
+
+def check_noise_profile(n: int, rates, depol_q16=0):
+    """``(rates, depol_q16)`` as a tuple of n + 1 ints and an int when they are a
+    valid profile of ``n`` parties: one integer rate in [0, 65535] per list row
+    (row 0 the commander's list, row 1 Lc, row g >= 2 lieutenant g) and
+    ``depol_q16`` in [0, 65535].  QbaError naming the row or ``depol_q16``
+    otherwise."""
+    try:
+        rs = list(rates)
+    except TypeError:
+        raise QbaError(f"noise profile: rates must be a sequence of {n + 1} integers, not {rates!r}") from None
+    if len(rs) != n + 1:
+        raise QbaError(f"noise profile: rates has {len(rs)} rows, n={n} needs {n + 1}")
+    return tuple(_q16(r, f"row {g}") for g, r in enumerate(rs)), _q16(depol_q16, "depol_q16")
+
+
+def noise_profile(n: int, all=0, rows=None, depol_q16=0):  # noqa: A002 (the CLI's word)
+    """The profile ``(rates, depol_q16)`` of ``n`` parties: every row at rate
+    ``all``, then ``rows`` ({row: rate}) over it."""
+    rates = [all] * (n + 1)
+    for g, k in (rows or {}).items():
+        if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or not 0 <= int(g) <= n:
+            raise QbaError(f"noise profile: row {g!r} outside [0, {n}]")
+        rates[int(g)] = k
+    return check_noise_profile(n, rates, depol_q16)
+
+
+def parse_noise_profile(n: int, text):
+    """``all:K,G:K,...,depol:K`` (K decimal or ``0x`` hex, G a row index; any
+    order, every item optional, a row overrides ``all``) as a checked profile.
+    An unknown key, a row > n or a repeated key is a QbaError naming it."""
+    if not isinstance(text, str):
+        return check_noise_profile(n, *text)
+    seen, rows, every, depol = set(), {}, 0, 0
+    for item in filter(None, (t.strip() for t in text.split(","))):
+        key, sep, val = item.partition(":")
+        key = key.strip()
+        if not sep:
+            raise QbaError(f"noise profile {text!r}: item {item!r} is not KEY:K")
+        try:
+            k = int(val, 0)
+        except ValueError:
+            raise QbaError(f"noise profile {text!r}: {key}: K is a number (0x... or decimal), not {val!r}") from None
+        if key in ("all", "depol"):
+            name = key
+        else:
+            try:
+                name = int(key, 10)
+            except ValueError:
+                raise QbaError(f"noise profile {text!r}: unknown key {key!r} (all, depol or a row index)") from None
+            if not 0 <= name <= n:
+                raise QbaError(f"noise profile {text!r}: row {name} outside [0, {n}]")
+        if name in seen:
+            raise QbaError(f"noise profile {text!r}: {'row ' if isinstance(name, int) else ''}{name} given twice")
+        seen.add(name)
+        if name == "all":
+            every = k
+        elif name == "depol":
+            depol = k
+        else:
+            rows[name] = k
+    return noise_profile(n, every, rows, depol)
+
+
+def format_noise_profile(profile) -> str:
+    """A profile in the normal form of :func:`parse_noise_profile`: ``all:K``
+    (the most common rate, the smaller one on a tie), the rows that differ in
+    ascending order, then ``depol:K``; every K in hex."""
+    rates, depol = profile
+    every = max(sorted(set(rates)), key=list(rates).count)
+    items = [f"all:{every:#x}"] + [f"{g}:{k:#x}" for g, k in enumerate(rates) if k != every]
+    return ",".join(items + [f"depol:{depol:#x}"])
+
+
+def noise_masks_profile(n: int, key: int, count: int, rates, depol_q16=0) -> np.ndarray:
+    """:func:`noise_masks` under a profile: uint8 [n+1, count], the value XORed
+    into group g of entry e.  With word(t) as there and j0 the lowest set bit
+    of any rate, 64 bits r start at 0 and take, for s = 0 .. 15 - j0,
+    ``x = word(2s) | word(2s+1) << 32; r = ((r | x) & M_s) | ((r & x) & ~M_s)``
+    where nibble g of M_s is 0xF when bit j0 + s of ``rates[g]`` is set: nibble
+    g goes through the ladder of its own rate (ANDs into 0 below its lowest
+    bit), so each of its bits is 1 with probability exactly ``rates[g] /
+    65536``, and with equal rates r is :func:`noise_masks`'s.  Then, when
+    ``depol_q16`` is not 0, ``d = philox4x32((e_lo, e_hi, DEPOL_CTR,
+    NOISE_TAG), key)`` and the entries with ``(d[0] & 0xFFFF) < depol_q16`` are
+    depolarised: ``r ^= d[2] | d[3] << 32``, a uniform value below w into every
+    group at once.  The mask of group g is ``(r >> 4g) & (w - 1)``.  The
+    all-zero profile draws nothing."""
+    rates, depol = check_noise_profile(n, rates, depol_q16)
+    g, w = n + 1, 1 << _nq(n)
+    count = int(count)
+    out = np.zeros((g, count), np.uint8)
+    anyr = 0
+    for k in rates:
+        anyr |= k
+    if not (anyr or depol):
+        return out
+    e = np.arange(count, dtype=np.uint64)
+    r = np.zeros(count, np.uint64)
+    key = int(key) & MASK64
+    if anyr:
+        j0 = (anyr & -anyr).bit_length() - 1
+        blk = None
+        for s in range(16 - j0):
+            if s % 2 == 0:
+                blk = _philox4x32_entries(e, s // 2, NOISE_TAG, key)
+            x = blk[2 * (s % 2)] | blk[2 * (s % 2) + 1] << np.uint64(32)
+            m = np.uint64(sum(0xF << (4 * i) for i, k in enumerate(rates) if (k >> (j0 + s)) & 1))
+            r = ((r | x) & m) | ((r & x) & ~m)
+    if depol:
+        d = _philox4x32_entries(e, DEPOL_CTR, NOISE_TAG, key)
+        hit = (d[0] & np.uint64(0xFFFF)) < np.uint64(depol)
+        r = np.where(hit, r ^ (d[2] | d[3] << np.uint64(32)), r)
+    for i in range(g):
+        out[i] = (r >> np.uint64(4 * i)) & np.uint64(w - 1)
+    return out
+
+
+def noisy_lists_profile(n: int, key: int, lists, rates, depol_q16=0) -> np.ndarray:
+    """``lists`` [n+1, count] with :func:`noise_masks_profile` XORed in (a new uint8 array)."""
+    L = np.array(lists, dtype=np.uint8).reshape(n + 1, -1)
+    return L ^ noise_masks_profile(n, key, L.shape[1], rates, depol_q16)
+
+
+def _no_profile(noise, what: str) -> None:
+    """ValueError when ``noise`` is a profile (not None): ``what`` is not built for one."""
+    if noise is not None:
+        raise ValueError(f"{what} is not built for a noise profile (noise=)")
+
+
+def _profile_alone(flip: int, coal: int, lossy: int, explain: int = 0) -> None:
+    """ValueError naming what a noise profile was combined with: a profile
+    replaces ``flip_q16``, and the coalition, lossy-network and trace kernels
+    take none."""
+    if flip:
+        raise ValueError(f"flip_q16={flip} with a noise profile (noise=): the profile holds the rates")
+    if coal:
+        _no_profile(True, f"a coalition (coalition={coal:#x})")
+    if lossy:
+        _no_profile(True, f"a lossy network (net={lossy:#x})")
+    if explain:
+        _no_profile(True, "explain (the trace kernels)")
 
 
 # ---------------------------------------------------------------------------
@@ -766,7 +931,7 @@ def _no_net(net, what: str) -> None:
 def run_host(n: int, sizeL: int, n_dishonest: int, n_inst: int, seed_base: int, engine, lists=None,
              party_cls=None, rng_factory: Optional[Callable] = None, flip_q16: int = 0,
              adversary: Optional[int] = None, coalition: Optional[int] = None,
-             net: Optional[int] = None) -> np.ndarray:
+             net: Optional[int] = None, noise=None) -> np.ndarray:
     """The specification of qba_protocol_batched: CountParty under
     ``protocol.run_local`` (LocalWorld's barrier-epoch delivery: a round's inbox
     is everything sent in the previous epoch, in (source, sequence) order,
@@ -795,10 +960,18 @@ def run_host(n: int, sizeL: int, n_dishonest: int, n_inst: int, seed_base: int, 
     ``adversary``, or the reference's rule); ``None`` and ``0`` are the perfect
     network and call what is called without the argument; ``party_cls`` may
     then be an observing :class:`NetParty` subclass.  Not with a coalition.
+
+    ``noise=(rates, depol_q16)``: a noise profile (:func:`noise_profile`) in
+    place of ``flip_q16``: :func:`noisy_lists_profile` of the lists the instance
+    would have used, then the same.  ``None`` calls what is called without the
+    argument.  Not with a non-zero ``flip_q16``, a coalition or a lossy network.
     """
     flip = _check_flip(flip_q16)
     coal = 0 if coalition is None else check_coalition(coalition)
     lossy = 0 if net is None else check_net(net)
+    prof = None if noise is None else check_noise_profile(n, *noise)
+    if prof is not None:
+        _profile_alone(flip, coal, lossy)
     if lossy:
         if coal:
             _no_net(lossy, "a coalition")
@@ -822,6 +995,9 @@ def run_host(n: int, sizeL: int, n_dishonest: int, n_inst: int, seed_base: int, 
         if flip and sizeL > 0:
             clean = engine.sample(n, key, 0, sizeL) if mine is None else np.asarray(mine)[:, :sizeL]
             mine = noisy_lists(n, key, _host_lists(clean, sizeL), flip)
+        elif prof is not None and sizeL > 0:
+            clean = engine.sample(n, key, 0, sizeL) if mine is None else np.asarray(mine)[:, :sizeL]
+            mine = noisy_lists_profile(n, key, _host_lists(clean, sizeL), *prof)
         cls = party_cls or CountParty
         if coal:  # what the traitors of this instance share
             cls = type(cls.__name__, (cls,), {"run_shared": CoalitionRun()})
@@ -1066,7 +1242,7 @@ def masks_from_lists(n: int, lists) -> dict:
 def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, packed: bool = True,
         batch: int = 4096, path: str = "tables", tally: bool = False, failures: int = 0, flip_q16: int = 0,
         adversary: Optional[int] = None, explain: int = 0, coalition: Optional[int] = None,
-        net: Optional[int] = None) -> dict:
+        net: Optional[int] = None, noise=None) -> dict:
     """``runs`` independent instances on the device, ``batch`` at a time, batch
     at offset ``off`` under key ``seed + off``; only the result rows are copied
     to the host.  Returns :func:`summarize` of all rows.
@@ -1107,9 +1283,21 @@ def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, pack
     ``net=word`` (``path="fused"`` only, without ``explain`` or ``coalition``):
     packets are lost in flight (:func:`net`); the decisions go through the
     lossy-network kernel as a curve of the one checkpoint ``sizeL``.  ``None``
-    and ``0`` call what is called without the argument."""
+    and ``0`` call what is called without the argument.
+
+    ``noise=(rates, depol_q16)`` (``path="fused"`` only; not with ``flip_q16``,
+    ``coalition``, a non-zero ``net`` or ``explain``): a noise profile
+    (:func:`noise_profile`); the decisions go through the noise-profile kernel
+    as a curve of the one checkpoint ``sizeL``.  ``None`` calls what is called
+    without the argument."""
     if path not in ("tables", "fused", "tables_noisy"):
         raise ValueError("path is 'tables', 'fused' or 'tables_noisy'")
+    if noise is not None:
+        if path != "fused":
+            _no_profile(noise, f"path={path!r}")
+        return curve(n, [sizeL], n_dishonest, runs, seed, engine, batch=batch, tally=tally, failures=failures,
+                     flip_q16=flip_q16, adversary=adversary, explain=explain, coalition=coalition, net=net,
+                     noise=noise)[int(sizeL)]
     if net is not None and check_net(net):
         if path != "fused":
             _no_net(net, f"path={path!r}")
@@ -1144,31 +1332,34 @@ def run(n: int, sizeL: int, n_dishonest: int, runs: int, seed: int, engine, pack
 
 def curve_host(n: int, counts, n_dishonest: int, n_inst: int, seed_base: int, engine, lists=None,
                flip_q16: int = 0, adversary: Optional[int] = None, coalition: Optional[int] = None,
-               net: Optional[int] = None) -> np.ndarray:
+               net: Optional[int] = None, noise=None) -> np.ndarray:
     """The specification of the curve calls: the stack of :func:`run_host` at
     each count of ``counts``, int32 [len(counts), n_inst, out_words(n)].
     Injected ``lists`` [n_inst, n+1, >= max(counts)] are truncated to
     ``[:, :, :c]`` for the count c.  ``flip_q16`` as in :func:`run_host` (the
     flips of entry e are the same at every count), ``adversary``,
-    ``coalition`` and ``net`` (a packet's loss does not depend on the count)."""
+    ``coalition`` and ``net`` (a packet's loss does not depend on the count),
+    and ``noise`` (a profile's masks of entry e are the same at every count)."""
     counts = [int(c) for c in counts]
     li = None if lists is None else np.asarray(lists)
-    noise = {"flip_q16": flip_q16} if flip_q16 else {}
+    how = {"flip_q16": flip_q16} if flip_q16 else {}
     if adversary is not None:
-        noise["adversary"] = adversary
+        how["adversary"] = adversary
     if coalition is not None:
-        noise["coalition"] = coalition
+        how["coalition"] = coalition
     if net is not None:
-        noise["net"] = net
+        how["net"] = net
+    if noise is not None:
+        how["noise"] = noise
     rows = [run_host(n, c, n_dishonest, n_inst, seed_base, engine, lists=None if li is None else li[:, :, :c],
-                     **noise)
+                     **how)
             for c in counts]
     return np.stack(rows) if rows else np.zeros((0, n_inst, out_words(n)), np.int32)
 
 
 def curve(n: int, counts, n_dishonest: int, runs: int, seed: int, engine, batch: int = 4096, tally: bool = False,
           failures: int = 0, flip_q16: int = 0, adversary: Optional[int] = None, explain: int = 0,
-          coalition: Optional[int] = None, net: Optional[int] = None) -> dict:
+          coalition: Optional[int] = None, net: Optional[int] = None, noise=None) -> dict:
     """The failure curve over sizeL: ``runs`` instances, ``batch`` at a time as
     :func:`run` keys them, each decided at every sizeL of the strictly
     increasing ``counts`` by one montecarlo_curve_sampled call per batch.
@@ -1180,13 +1371,19 @@ def curve(n: int, counts, n_dishonest: int, runs: int, seed: int, engine, batch:
     montecarlo_curve_sampled_coal call per batch instead; ``None`` and ``0``
     call what is called without it.  ``net=word`` (not with ``explain`` or
     ``coalition``): one montecarlo_curve_sampled_net call per batch instead;
-    ``None`` and ``0`` call what is called without it."""
+    ``None`` and ``0`` call what is called without it.  ``noise=(rates,
+    depol_q16)`` (not with ``flip_q16``, ``coalition``, a non-zero ``net`` or
+    ``explain``): one montecarlo_curve_sampled_nprof call per batch instead;
+    ``None`` calls what is called without it."""
     counts = [int(c) for c in counts]
+    prof = None if noise is None else check_noise_profile(n, *noise)
     noise = {"flip_q16": _check_flip(flip_q16)} if flip_q16 else {}
     if adversary is not None:
         noise["adversary"] = check_adversary(adversary)
     coal = 0 if coalition is None else check_coalition(coalition)
     lossy = 0 if net is None else check_net(net)
+    if prof is not None:
+        _profile_alone(noise.get("flip_q16", 0), coal, lossy, explain)
     if lossy and coal:
         _no_net(lossy, "a coalition")
     if lossy and explain:
@@ -1197,6 +1394,8 @@ def curve(n: int, counts, n_dishonest: int, runs: int, seed: int, engine, batch:
         engine._check_curve(n, n_dishonest, 0, counts)  # before any device buffer: an empty list has no slice
 
     def decide(key, b, **into):
+        if prof is not None:
+            return engine.montecarlo_curve_sampled_nprof(n, n_dishonest, key, b, counts, noise=prof, **into, **noise)
         if lossy:
             return engine.montecarlo_curve_sampled_net(n, n_dishonest, key, b, counts, net=lossy, **into, **noise)
         if coal:
@@ -1239,7 +1438,7 @@ def sweep_host(n: int, counts, scenarios, n_inst: int, seed_base: int, engine, l
 
 
 def sweep(n: int, counts, scenarios, runs: int, seed: int, engine, batch: int = 4096, tally: bool = False,
-          failures: int = 0, flip_q16: int = 0, explain: int = 0, net: Optional[int] = None) -> dict:
+          failures: int = 0, flip_q16: int = 0, explain: int = 0, net: Optional[int] = None, noise=None) -> dict:
     """:func:`curve` under every scenario ``(n_dishonest, word)`` of
     ``scenarios`` at once: ``runs`` instances, ``batch`` at a time as
     :func:`run` keys them, each sampled and distilled once and decided at every
@@ -1249,8 +1448,10 @@ def sweep(n: int, counts, scenarios, runs: int, seed: int, engine, batch: int = 
     summary is that of ``curve(..., n_dishonest, adversary=word)`` at that
     sizeL.  ``tally``, ``failures``, ``flip_q16`` and ``explain`` as there (one
     trace call per slice).  Duplicate scenarios would share a key: ValueError.
-    ``net`` is taken only to be refused when it is a non-zero network word."""
+    ``net`` is taken only to be refused when it is a non-zero network word,
+    ``noise`` when it is a noise profile."""
     _no_net(net, "a sweep")
+    _no_profile(noise, "a sweep")
     counts = [int(c) for c in counts]
     sc = _scenarios(n, scenarios)
     if len(set(sc)) != len(sc):
@@ -1306,7 +1507,7 @@ def grid_host(n: int, counts, scenarios, n_inst: int, seed_base: int, engine, li
 
 
 def grid(n: int, counts, scenarios, runs: int, seed: int, engine, batch: int = 4096, tally: bool = False,
-         failures: int = 0, flip_q16: int = 0) -> dict:
+         failures: int = 0, flip_q16: int = 0, noise=None) -> dict:
     """:func:`curve` under every scenario ``(n_dishonest, word, net)`` of
     ``scenarios`` at once: ``runs`` instances, ``batch`` at a time as
     :func:`run` keys them, each sampled and distilled once and decided at every
@@ -1316,7 +1517,9 @@ def grid(n: int, counts, scenarios, runs: int, seed: int, engine, batch: int = 4
     each summary is that of ``curve(..., n_dishonest, adversary=word, net=net)``
     at that sizeL.  ``tally``, ``failures`` and ``flip_q16`` as there.  There is
     no ``explain``: the trace kernels are not built for a lossy network.
-    Duplicate scenarios would share a key: ValueError."""
+    Duplicate scenarios would share a key: ValueError.  ``noise`` is taken only
+    to be refused when it is a noise profile."""
+    _no_profile(noise, "a grid")
     counts = [int(c) for c in counts]
     sc = _grid_scenarios(n, scenarios)
     if len(set(sc)) != len(sc):
@@ -1625,7 +1828,7 @@ def trace_net_host(n: int, sizeL: int, n_dishonest: int, indices, seed_base: int
 
 
 def replay(n: int, sizeL: int, n_dishonest: int, indices, seed: int, engine, flip_q16: int = 0,
-           adversary: Optional[int] = None, net: Optional[int] = None, cap: int = 1024) -> dict:
+           adversary: Optional[int] = None, net: Optional[int] = None, cap: int = 1024, noise=None) -> dict:
     """The transcripts of the runs ``indices`` of a ``run`` / ``curve`` / ``grid``
     item under ``seed`` (key = seed + index, the rule of ``failed_runs``), as the
     device re-runs them: one trace call -- ``montecarlo_trace_sampled_net`` when
@@ -1634,7 +1837,9 @@ def replay(n: int, sizeL: int, n_dishonest: int, indices, seed: int, engine, fli
     tensor (a tally's capture row).  Returns ``{"indices", "rows", "counts",
     "events"}`` as host arrays, slot j belonging to ``indices[j]``;
     :func:`format_trace` renders a slot.  A coalition's runs have no transcript:
-    there is no argument for its word."""
+    there is no argument for its word, and ``noise`` is taken only to be
+    refused when it is a noise profile."""
+    _no_profile(noise, "replay (the trace kernels)")
     lossy = 0 if net is None else check_net(net)
     if lossy:
         out = engine.montecarlo_trace_sampled_net(n, n_dishonest, seed, indices, sizeL, cap=cap, flip_q16=flip_q16,

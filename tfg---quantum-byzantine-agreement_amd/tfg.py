@@ -136,6 +136,13 @@ def _args(argv):
                          "K / 65536 (K decimal or 0x hex; montecarlo.net), with :cmd the commander's packets too; "
                          "implies --fused; the summary lines end in drop=K/65536 [cmd]; not with --collude, --sweep, "
                          "--explain or --tables")
+    ap.add_argument("--noise", default=None, metavar="all:K,G:K,...,depol:K",
+                    help="with --runs: a noise profile (montecarlo.noise_profile): every measured bit of list row G "
+                         "flips with probability K / 65536 (row 0 the commander's list, 1 Lc, G >= 2 lieutenant G; "
+                         "all:K sets every row, a row given after it overrides), and with depol:K a whole entry is "
+                         "depolarised with probability K / 65536 (K decimal or 0x hex); implies --fused; the summary "
+                         "lines end in noise=SPEC in normal form; not with --flip, --collude, --drop, --sweep, --grid, "
+                         "--explain, --tables or --replay")
     ap.add_argument("--sweep", default=None, metavar="K:POLICY,...",
                     help="with --runs: decide every instance under each of these scenarios in one pass per batch "
                          "(montecarlo.sweep; at most 16, and 32 lines with --curve): K traitors following POLICY "
@@ -161,6 +168,22 @@ def _args(argv):
                     help="in-process exact mode: send the lists in the reference's int64-per-bit wire layout "
                          "(tfg.py:142-161) instead of handing each rank its device row")
     a = ap.parse_args(argv)
+    if a.noise is not None:
+        given = [flag for flag, on in (("--flip", a.flip is not None), ("--collude", a.collude is not None),
+                                       ("--drop", a.drop is not None), ("--sweep", a.sweep is not None),
+                                       ("--grid", a.grid is not None), ("--explain", a.explain),
+                                       ("--tables", a.tables), ("--replay", a.replay is not None)) if on]
+        if given:
+            ap.error(f"--noise: not with {', '.join(given)} (a profile holds the flip rates itself, and the "
+                     "coalition, lossy-network, sweep, grid, trace and tables paths are not built for one)")
+        if a.runs is None:
+            ap.error("--noise needs --runs")
+        from . import montecarlo
+        try:
+            a.noise = montecarlo.parse_noise_profile(a.parties, a.noise)
+        except montecarlo.QbaError as e:
+            ap.error(f"--noise: {e}")
+        a.fused = True
     if a.replay is not None:
         given = [flag for flag, on in (("--runs", a.runs is not None), ("--collude", a.collude is not None),
                                        ("--sweep", a.sweep is not None), ("--grid", a.grid is not None),
@@ -403,6 +426,9 @@ def _montecarlo(a, eng, size_l) -> int:
     if a.drop is not None:
         how["net"] = a.drop
         noise += f" drop={a.drop & 0xFFFF}/65536" + (" cmd" if a.drop >> 16 else "")
+    if a.noise is not None:
+        how["noise"] = a.noise
+        noise += f" noise={montecarlo.format_noise_profile(a.noise)}"
     if a.grid is not None:
         grid = montecarlo.grid(a.parties, a.curve if a.curve is not None else [size_l], a.grid, a.runs, seed, eng,
                                batch=a.batch, **how)

@@ -81,6 +81,17 @@ instances x n = 7 x sizeL = 1e5, 2 dishonest, on one GPU.
       runs another protocol: its times are reported without a verdict, its
       success counts beside them.
 
+  --noise all:K,G:K,...,depol:K  (repeatable) another mode, per --sizeL: the
+      noise-profile call (qba_montecarlo_curve_sampled_nprof, one checkpoint)
+      under each profile given, beside the _adv curve call at flip_q16 = the OR
+      of the profile's rates (the same ladder steps; 0 for the all-zero and the
+      depol-only profiles), which is timed first and again last in the same
+      session.  A uniform profile without depol must give that call's rows:
+      unequal rows are an error.  Every profile's success count stands beside
+      its times.  --noise-split M adds the success counts with the total noise
+      (n + 1) * M on all rows, on the commander's rows, on the honest parties'
+      rows and on the traitors' rows of each instance.
+
   --trace  another mode, per --sizeL: the montecarlo_trace_sampled call at 16
       and at --instances indices (cap 256, the reference policy word) beside
       montecarlo_sampled(..., adversary=0xF) of the same number of instances --
@@ -106,6 +117,8 @@ import statistics
 import sys
 import time
 from pathlib import Path
+
+import numpy as np
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
@@ -167,6 +180,13 @@ def main(argv=None) -> int:
                     help="time the lossy-network call at net = 0 and at each of these network words beside the "
                          "_adv curve call of one checkpoint, at each --sizeL, under the policies of --adversary "
                          "(default reference and reorder_low); nothing else is measured")
+    ap.add_argument("--noise", action="append", default=None, metavar="all:K,G:K,...,depol:K",
+                    help="time the noise-profile call under each of these profiles beside the _adv curve call of one "
+                         "checkpoint at flip_q16 = the OR of the profile's rates, at each --sizeL, under the first "
+                         "policy of --adversary (default reference); repeatable; nothing else is measured")
+    ap.add_argument("--noise-split", type=lambda t: int(t, 0), default=0, metavar="M",
+                    help="with --noise: also the success counts with the total noise (n + 1) * M on all rows, on the "
+                         "commander's rows, on the honest parties' rows and on the traitors' rows of each instance")
     ap.add_argument("--trace", action="store_true",
                     help="time montecarlo_trace_sampled at 16 and at --instances indices beside montecarlo_sampled "
                          "with the reference policy word at the same shapes, and the host wall time of trace_host "
@@ -174,6 +194,10 @@ def main(argv=None) -> int:
                          "each network word beside montecarlo_curve_sampled_net and montecarlo_trace_sampled; "
                          "nothing else is measured")
     a = ap.parse_args(argv)
+    if a.noise and (a.trace or a.collude or a.drop or a.grid or a.sweep or a.flip or a.curve or a.tally or a.tables):
+        ap.error("--noise goes with --sizeL, --adversary and --noise-split alone")
+    if a.noise_split and not a.noise:
+        ap.error("--noise-split needs --noise")
     if a.trace and (a.sweep or a.adversary or a.flip or a.curve or a.tally or a.tables):
         ap.error("--trace goes with --sizeL alone")
     if a.collude and (a.trace or a.sweep or a.flip or a.curve or a.tally or a.tables):
@@ -190,7 +214,9 @@ def main(argv=None) -> int:
         ap.error("--tables needs --flip and goes with neither --curve nor --tally")
 
     eng = importlib.import_module(f"{PKG}.engine").Engine(0)
-    if a.grid:
+    if a.noise:
+        lines = [json.dumps(_measure_noise(a, eng, size_l)) for size_l in (a.sizeL or [100_000])]
+    elif a.grid:
         shapes = [[s] for s in (a.sizeL or [])] + [sorted({int(c) for c in text.split(",")}) for text in a.curve or []]
         lines = [json.dumps(_measure_grid(a, eng, counts, text)) for text in a.grid for counts in shapes or [[100_000]]]
     elif a.trace and a.drop:
@@ -496,6 +522,79 @@ def _measure_drop(a, eng, size_l) -> dict:
         r["perfect_network_slower"] = z["min_ms"] > hi
         r["perfect_network_faster"] = z["max_ms"] < lo
         res["policies"][policy] = r
+    return res
+
+
+def _measure_noise(a, eng, size_l) -> dict:
+    """--noise: per profile, the noise-profile call beside the _adv curve call of one checkpoint at
+    flip_q16 = the OR of the profile's rates (the same ladder steps and Philox blocks; 0 for the all-zero and the
+    depol-only profiles).  Every baseline is timed first, and again last; a uniform profile without depol must give
+    its baseline's rows.  With --noise-split M: the success counts with the total noise (n + 1) * M on all rows, on
+    the commander's rows 0 and 1, on the honest parties' rows and on the traitors' rows of each instance (one call
+    per instance: the traitors differ from key to key)."""
+    import torch
+    mc = importlib.import_module(f"{PKG}.montecarlo")
+    n, nd, inst = a.parties, a.dishonest, a.instances
+    adv = mc.parse_adversary((a.adversary or ["reference"])[0])
+    res = {"config": {"n": n, "sizeL": size_l, "dishonest": nd, "instances": inst, "seed": a.seed, "adv": f"{adv:#x}",
+                      "device": torch.cuda.get_device_name(0)}, "baselines": {}, "profiles": {}}
+    profs = {mc.format_noise_profile(p): p for p in (mc.parse_noise_profile(n, s) for s in a.noise)}
+    k_of = lambda p: int(np.bitwise_or.reduce(np.array(p[0])))  # noqa: E731
+    rows = eng.montecarlo_curve_sampled(n, nd, a.seed, inst, [size_l], adversary=adv)
+    refs = {}
+
+    def base(k):
+        return lambda: eng.montecarlo_curve_sampled(n, nd, a.seed, inst, [size_l], rows, flip_q16=k, adversary=adv)
+    for k in sorted({k_of(p) for p in profs.values()}):
+        t = _events(base(k), a.warmup, a.repeats)
+        refs[k] = rows.clone()
+        t["successes"] = int(rows[0, :, 0].sum())
+        res["baselines"][f"{k:#x}"] = {"first": t}
+    for name, p in profs.items():
+        k = k_of(p)
+        t = _events(lambda: eng.montecarlo_curve_sampled_nprof(n, nd, a.seed, inst, [size_l], rows, adversary=adv,
+                                                               noise=p), a.warmup, a.repeats)
+        t["baseline_flip_q16"] = f"{k:#x}"
+        t["successes"] = int(rows[0, :, 0].sum())
+        t["empty_vi_runs"] = int((rows[0, :, 2] != 0).sum())
+        if len(set(p[0])) == 1 and not p[1]:
+            t["rows_equal_baseline"] = bool(torch.equal(rows, refs[k]))
+            if not t["rows_equal_baseline"]:
+                raise SystemExit(f"the uniform profile {name} does not give the _adv curve call's rows at "
+                                 f"flip_q16={k:#x} (n={n}, sizeL={size_l})")
+        res["profiles"][name] = t
+    for k in sorted({k_of(p) for p in profs.values()}):
+        b = res["baselines"][f"{k:#x}"]
+        b["last"] = _events(base(k), a.warmup, a.repeats)
+        lo_med = min(b["first"]["median_ms"], b["last"]["median_ms"])
+        b["spread_at_median"] = abs(b["first"]["median_ms"] - b["last"]["median_ms"]) / lo_med
+        lo, hi = min(b["first"]["min_ms"], b["last"]["min_ms"]), max(b["first"]["max_ms"], b["last"]["max_ms"])
+        for t in res["profiles"].values():
+            if t["baseline_flip_q16"] == f"{k:#x}":
+                t["over_baseline_at_median"] = t["median_ms"] / lo_med
+                t["ranges_overlap"] = not (t["min_ms"] > hi or t["max_ms"] < lo)
+    if a.noise_split:
+        m, total = a.noise_split, (n + 1) * a.noise_split
+        clean = eng.montecarlo_curve_sampled(n, nd, a.seed, inst, [size_l], adversary=adv).cpu().numpy()[0]
+        owner = [1, 1] + list(range(2, n + 1))  # the party a list row belongs to
+        split = {"mean_rate": f"{m:#x}"}
+
+        def count(rows_of):
+            one = torch.empty((1, 1, 4 + 5 * (n + 1)), dtype=torch.int32, device=eng.device)
+            acc = torch.zeros((), dtype=torch.int64, device=eng.device)
+            for i in range(inst):
+                pick = rows_of(int(clean[i, 1]))
+                rate = min(total // len(pick), 0xFFFF) if pick else 0
+                prof = mc.noise_profile(n, 0, {g: rate for g in pick})
+                eng.montecarlo_curve_sampled_nprof(n, nd, a.seed + i, 1, [size_l], one, adversary=adv, noise=prof)
+                acc += one[0, 0, 0]
+            return int(acc.item())
+        split["uniform"] = count(lambda dis: list(range(n + 1)))
+        split["commander_only"] = count(lambda dis: [0, 1])
+        split["honest_only"] = count(lambda dis: [g for g in range(n + 1) if not (dis >> owner[g]) & 1])
+        split["traitors_only"] = count(lambda dis: [g for g in range(n + 1) if (dis >> owner[g]) & 1])
+        split["noiseless"] = int(clean[:, 0].sum())
+        res["split"] = split
     return res
 
 
